@@ -1,11 +1,21 @@
 """bench.py - rays/sec of the NeuRay per-ray render path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (coarse + fine render_impl over every ray batch) over one synthetic
 "lego-800" image: 800x800 = 640,000 rays, 8 reference views, 64 coarse + 32 fine samples (the configuration
 BASELINE.json's metric is quoted on), seeded random weights and feature maps; inputs are
 resident in HBM before the timed region.
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the outputs (`--dump-outputs`) and
+the JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, ...).
+Everything else described below - the roofline of the point kernel (HIP events + one extra image for the slot counters),
+the baselines, parity legs, other arithmetics / sizes / workloads and the N > 1 side legs - runs only with `--full`.
+
+`--dump-outputs DIR` writes what the last timed step returned (`renderer.render()`'s tensors for the whole image) as
+DIR/<key>.npy in float32 (float64 stays float64; boolean masks as 0 / 1).  The inputs are seeded, so the same arguments
+give the same inputs on every run and two builds can be compared output by output.  Above 64 MB in all, a fixed seeded
+sample of the rays is written instead, with their indices in DIR/ray_index.npy.
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL).  Started without a launcher (`WORLD_SIZE` unset),
 `python bench.py --gpus N` re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -14,14 +24,14 @@ WORLD_SIZE == N.  Images are sharded across ranks (no data-path collective; rays
 scaling; the timed region is bracketed by barrier + synchronize and the max over ranks is taken.  After the timed
 region an N > 1 run adds two side legs to the line: `split_image` (ONE image split over the ranks + one fused all-gather
 of the tiles) and `train_ddp` (forward + backward + ONE flattened gradient all-reduce per step); they run after the headline is in
-hand and under a watchdog (`--side-leg-timeout`), so a rank lost inside one costs the side legs, not the line.
+hand and under a watchdog (`--side-leg-timeout`), so a rank lost inside one costs the side legs, not the line (`--full` only).
 
-One JSON line is printed by rank 0.  `roofline` is for the dominant kernel (the MFMA point kernel):
+One JSON line is printed by rank 0.  `roofline` (`--full`) is for the dominant kernel (the MFMA point kernel):
 achieved = algorithmic FLOPs per launch / average launch duration (HIP events on the launch stream).
 `cpu_baseline` times the golden-checked eager-PyTorch port of the reference's op sequence (oracle/torch_eager_port.py;
 the reference tree itself does not exist on the GPU box; where it exists, the port runs the same batches within ~10 % of the reference
 itself - 0.83 ... 1.02 x on a shared host - with identical pixels: tools/port_vs_reference_cpu.py) on the host - with torch.set_num_threads(physical cores) and,
-on a many-core host, with 16 threads; the faster one is `value` - on a bounded sample of the same workload.  At N = 1 side measurements ride along (reported baselines, not the metric):
+on a many-core host, with 16 threads; the faster one is `value` - on a bounded sample of the same workload.  At N = 1 with `--full` side measurements ride along (reported baselines, not the metric):
 `eager_torch_baseline` (the same port on the same GPU - the stand-in for "the reference on stock PyTorch-ROCm"),
 `numpy_oracle` (parity of the rendered image against the numpy oracle + its speed; `parity.full_image`, round 5: ALL rays of the image
 against that port on the GPU, the rays it disputes re-rendered by the numpy oracle), `extra` (64+64 samples, the
@@ -104,6 +114,31 @@ def render_image(renderer, tq, tr, split=False):
             from neuray_amd import parallel
             return parallel.render_image_sharded(renderer, q, r)
         return renderer.render(q, r, False)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory, seed=0):
+    """--dump-outputs: the tensors render_image() returned, as <directory>/<key>.npy (float64 stays float64, everything else
+    float32).  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the rays (axis 1 of every output) with its indices in
+    ray_index.npy.  -> names written"""
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            arrays[k] = v.detach().cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = next(iter(arrays.values())).shape[1]
+        assert all(a.shape[1] == n for a in arrays.values()), {k: a.shape for k, a in arrays.items()}
+        keep = int(DUMP_LIMIT_BYTES // (total / n + 8))          # (+ 8 bytes per ray: its float64 index)
+        idx = np.sort(np.random.RandomState(seed).choice(n, keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[:, idx]) for k, a in arrays.items()}
+        arrays['ray_index'] = idx.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + '.npy'), a)
+    return sorted(arrays)
 
 
 def host_cpu():
@@ -1083,7 +1118,13 @@ def main(argv=None):
     ap.add_argument('--emulator-lib', default=None, help='TEST HOOK: CPU emulator build of the kernels, gloo, tiny image')
     ap.add_argument('--size', type=int, nargs=2, default=None, metavar=('H', 'W'), help='test hook: image size (default 800 800)')
     ap.add_argument('--leg', default=None, help='internal: run ONE training-step side leg in this (fresh) process and print its JSON')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: roofline, baselines, parity legs, other arithmetics / sizes / workloads, N > 1 side legs')
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.arith is None:                                         # (the emulator smoke of the launcher path keeps the cheaper arithmetic)
         args.arith = 'f32' if args.emulator_lib else 'x3'
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')       # multi-process GPU work: the host driver only supports dmabuf IPC (RCCL)
@@ -1142,13 +1183,15 @@ def main(argv=None):
             dist.barrier()
             sync()
 
-    # the share of (tile, view) slots the point kernel runs / skips: counted by the kernel itself in ONE extra image outside the timed
-    # region (deterministic per image; the counters cost two atomics per workgroup, which the timed launches do not pay)
-    slot_stats = torch.zeros(2, dtype=torch.int64, device=device) if device.type == 'cuda' else None
-    eng.slot_stats = slot_stats
-    render_image(renderer, tq, tr, split)
-    eng.slot_stats = None
-    eng.timing = []
+    slot_stats = None
+    if args.full:
+        # the share of (tile, view) slots the point kernel runs / skips: counted by the kernel itself in ONE extra image outside the timed
+        # region (deterministic per image; the counters cost two atomics per workgroup, which the timed launches do not pay)
+        slot_stats = torch.zeros(2, dtype=torch.int64, device=device) if device.type == 'cuda' else None
+        eng.slot_stats = slot_stats
+        render_image(renderer, tq, tr, split)
+        eng.slot_stats = None
+        eng.timing = []                    # HIP events around the launches of the timed region: the roofline's kernel durations
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -1160,6 +1203,8 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     timing, eng.timing = eng.timing, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     line = None
     if rank == 0:
@@ -1180,7 +1225,7 @@ def main(argv=None):
                        'ray_batch': cfg['ray_batch_num'], 'parallelism': ('one image split over %d GPUs, all-gather of tiles' % world) if split else
                                       ('images sharded over %d GPU(s), no collective' % world)},
         }
-        if device.type == 'cuda':
+        if args.full and device.type == 'cuda':
             # dominant kernel: the point kernel.  Duration from HIP events on the launch stream.
             pts = [(e0.elapsed_time(e1) * 1e-3, n) for name, e0, e1, n in timing if name == 'points']
             rays_k = [e0.elapsed_time(e1) * 1e-3 for name, e0, e1, n in timing if name == 'rays']
@@ -1247,7 +1292,7 @@ def main(argv=None):
                                                       "splits, ELU, blends, statistics (DESIGN.md 4.12).  The maps are L2 / Infinity-Cache resident (roofline.traffic), so "
                                                       "the demand rate is a cache-path figure, not an HBM one",
                                 'point_kernel_share_of_step': t_pts / dt, 'ray_kernel_share_of_step': sum(rays_k) / dt}
-        else:
+        elif args.full:
             line['roofline'] = None
 
     # ---- N > 1 side legs: collectives, every rank takes part.  They run AFTER the headline is in hand and under a watchdog: a rank
@@ -1281,7 +1326,7 @@ def main(argv=None):
         watchdog = threading.Timer(limit, expired)
         watchdog.daemon = True
         watchdog.start()
-    if world > 1 and not args.no_side_legs:
+    if world > 1 and args.full and not args.no_side_legs:
         legs = {}
         if not split:
             c2, r2, _, _, _, tq2, tr2 = build_case(device, args.fine_samples, seed=0, test_lib=emu)
@@ -1298,7 +1343,7 @@ def main(argv=None):
                 put(k_, v_)
 
     others = {}
-    if rank == 0 and world == 1 and emu is None and device.type == 'cuda':
+    if rank == 0 and world == 1 and emu is None and device.type == 'cuda' and args.full:
         if args.arith != 'f32':       # the fp32-MFMA line, next to the headline either way (VERDICT r5 credit rule)
             res = side(fp32_mfma_leg, device, args.fine_samples, tq, tr, args.steps, value)
             if isinstance(res, tuple):
@@ -1306,7 +1351,7 @@ def main(argv=None):
                 others['ours_fp32_mfma'] = res[1]
             else:
                 put('fp32_mfma', res)
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and emu is None and not args.no_eager_baseline and not args.no_cpu_baseline:
             # the whole-step training legs first: they are host-sensitive (host time ~ device time), and after the CPU baselines' minute
             # of all-core work below the host's single-thread speed stays depressed for a while - measured after them the generalisation
@@ -1345,7 +1390,7 @@ def main(argv=None):
             put('bf16_variant', side(bf16_variant_timing, device, args.fine_samples, tq, tr, out['pixel_colors_nr_fine'].cpu().numpy()))
             put('bf16x3_split_variant', side(bf16_variant_timing, device, args.fine_samples, tq, tr, out['pixel_colors_nr_fine'].cpu().numpy(),
                                              2, 'bf16x3'))
-    if rank == 0 and line is not None:
+    if rank == 0 and line is not None and args.full:
         # the scalars a reader of the LAST kilobytes of this (long) line needs: the driver keeps only the tail of stdout
         def pick(d, *path):
             for k_ in path:

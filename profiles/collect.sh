@@ -7,9 +7,9 @@ TAG=${1:-prof}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-eager-baseline"
+BENCH="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-eager-baseline"
 
-timeout 300 python bench.py --steps 5 --warmup 2 > "$OUT/bench.log" 2>&1
+timeout 300 python bench.py --full --steps 5 --warmup 2 > "$OUT/bench.log" 2>&1
 tail -1 "$OUT/bench.log" > "$OUT/bench.json"
 
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- $BENCH > "$OUT/trace.log" 2>&1

@@ -4,7 +4,7 @@
 # (A pass with the TA_*BUSY / TA_*STALLED counters aborts rocprofv3 7.2 on this image - signal 6 - and is left out.)
 set -u
 OUT=gpurun_out/${1:-gather}; mkdir -p $OUT; export TMPDIR=/tmp
-BENCH="python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-eager-baseline"
+BENCH="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-eager-baseline"
 i=0
 for set in "TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_PENDING_STALL_CYCLES_sum" \
            "GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VMEM_RD" \

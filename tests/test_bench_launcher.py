@@ -1,7 +1,8 @@
 """The N > 1 path of bench.py itself on CPU (world size 2, gloo, kernels on the CPU emulator through bench.py's
 `--emulator-lib` test hook): `python bench.py --gpus 2` with no launcher must start two ranks by itself, report the world
 size the process group saw, shard images (timed region), split one image + all-gather the tiles, and run data-parallel
-training steps with one gradient all-reduce - and it must refuse to print a line with the wrong `n_gpus`."""
+training steps with one gradient all-reduce (the side legs: `--full`) - and it must refuse to print a line with the wrong `n_gpus`.
+A plain run prints the headline alone and writes its outputs with `--dump-outputs`."""
 import json
 import os
 import subprocess
@@ -31,7 +32,7 @@ def emu_path():
 
 
 def test_gpus_2_without_a_launcher_starts_two_ranks(emu_path):
-    p = run_bench(['--gpus', '2', '--steps', '1', '--warmup', '1', '--emulator-lib', emu_path])
+    p = run_bench(['--gpus', '2', '--steps', '1', '--warmup', '1', '--emulator-lib', emu_path, '--full'])
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, p.stdout                  # ONE JSON line, printed by rank 0 only
@@ -48,7 +49,8 @@ def test_gpus_2_without_a_launcher_starts_two_ranks(emu_path):
 def test_a_rank_lost_inside_a_side_leg_costs_the_side_legs_not_the_line(emu_path):
     """rank 1 raises inside the first side leg and never joins another collective: rank 0 is left waiting in one.  The watchdog must
     print the (complete) headline line once and end every rank with exit code 0."""
-    p = run_bench(['--gpus', '2', '--steps', '1', '--warmup', '0', '--emulator-lib', emu_path, '--fail-leg-on-rank', '1', '--side-leg-timeout', '12'],
+    p = run_bench(['--gpus', '2', '--steps', '1', '--warmup', '0', '--emulator-lib', emu_path, '--fail-leg-on-rank', '1', '--side-leg-timeout', '12',
+                   '--full'],
                   timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
@@ -66,6 +68,28 @@ def test_split_image_as_the_timed_region(emu_path):
     assert abs(line['value'] - 16 * 24 / (line['ms_per_step'] * 1e-3)) <= 1e-6 * line['value']
 
 
+def test_plain_run_is_the_headline_and_dumps_identical_outputs(emu_path, tmp_path):
+    """without --full: the headline line only (no roofline, baselines or side legs); --dump-outputs writes the last timed step's
+    outputs as float32 .npy files, and two runs with other step counts see the same inputs, so they write the same arrays"""
+    import numpy as np
+    dumps = []
+    for steps, warmup in ((1, 0), (2, 1)):
+        d = tmp_path / ('out%d' % steps)
+        p = run_bench(['--gpus', '1', '--steps', str(steps), '--warmup', str(warmup), '--emulator-lib', emu_path, '--dump-outputs', str(d)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, p.stdout
+        line = json.loads(lines[0])
+        assert line['steps'] == steps and line['warmup'] == warmup and line['unit'] == 'rays/s' and line['higher_is_better'] is True
+        assert abs(line['value'] - 16 * 24 / (line['ms_per_step'] * 1e-3)) <= 1e-6 * line['value']
+        assert not {'roofline', 'summary', 'cpu_baseline', 'split_image', 'train_ddp'} & set(line), sorted(line)
+        dumps.append({f: np.load(str(d / f)) for f in os.listdir(str(d))})
+    assert set(dumps[0]) == {'pixel_colors_nr.npy', 'pixel_colors_nr_fine.npy', 'ray_mask.npy', 'ray_mask_fine.npy'}, sorted(dumps[0])
+    for f, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.shape[1] == 16 * 24 and np.isfinite(a).all(), f
+        assert np.array_equal(a, dumps[1][f]), f
+
+
 def test_refuses_a_wrong_world_size():
     p = run_bench(['--gpus', '2', '--steps', '1'])            # no GPU in this container, no emulator hook
     assert p.returncode != 0 and 'GPU(s) visible' in p.stderr and '{' not in p.stdout
@@ -78,7 +102,7 @@ def test_refuses_a_wrong_world_size():
 def test_gpus_8_world_size_of_the_target_node(emu_path):
     """the driver's largest launch (8 ranks, one per GPU of an MI355X node) on gloo + emulator: eight ranks start, the line
     reports 8, the split image (16 x 24 = 384 rays, 48 per rank) is gathered whole, replicas stay identical"""
-    p = run_bench(['--gpus', '8', '--steps', '1', '--warmup', '0', '--emulator-lib', emu_path],
+    p = run_bench(['--gpus', '8', '--steps', '1', '--warmup', '0', '--emulator-lib', emu_path, '--full'],
                   env={'NEURAY_EMU_THREADS': '1', 'OMP_NUM_THREADS': '1'}, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]

@@ -1,10 +1,11 @@
 """on-disk scene adapters (neuray_amd/database.py) for the two evaluation formats of BASELINE.json's
 configs.  A fixture writes a small nerf_synthetic scene (transforms_*.json, RGBA PNGs, COLMAP depth maps) and a small
 llff_colmap scene (COLMAP binary model, cached images, depth_range.npy, depth maps) to a temporary directory; the adapters
-are compared accessor by accessor with the REFERENCE's own database classes reading the same files (where the reference
-tree exists: its cv2 / skimage imports are the stubs of tests/golden/ref_harness.py, `imread` is pointed at PIL), and
+are compared accessor by accessor with the REFERENCE's own database classes reading the same files (their values recorded in
+tests/golden/case_database_reference.npz: the `ref_db` fixture says how they were produced), and
 render.py's eval loop (prepare_render_info -> select_working_views_db -> build_imgs_info -> renderer -> imsave) runs end to
 end on the on-disk scene through the kernels on the emulator."""
+import hashlib
 import json
 import os
 import struct
@@ -14,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import GOLDEN_DIR, ROOT
 from emu_util import emu_lib
 from neuray_amd import database as D
 from neuray_amd import pipeline, synthetic
@@ -127,11 +128,110 @@ def scenes(tmp_path_factory):
             'dtu': write_dtu_test(os.path.join(root, 'dtu_test'))}
 
 
+REF_DB_GOLDEN = os.path.join(GOLDEN_DIR, 'case_database_reference.npz')
+
+
+class Digest:
+    """a recorded array too large to store: shape, dtype and sha256 of its bytes (`same` compares an array against it exactly)"""
+    def __init__(self, shape, dtype, sha):
+        self.shape, self.dtype, self.sha = tuple(shape), np.dtype(dtype), sha
+
+    def matches(self, a):
+        a = np.asarray(a)
+        return a.shape == self.shape and a.dtype == self.dtype and hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest() == self.sha
+
+
+def _encode(v, arrays):
+    if v is None:
+        return {'none': 1}
+    if isinstance(v, np.ndarray):
+        if v.nbytes <= 4096:
+            arrays['a%d' % len(arrays)] = v
+            return {'array': 'a%d' % (len(arrays) - 1)}
+        return {'digest': [list(v.shape), v.dtype.str, hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest()]}
+    if isinstance(v, (list, tuple)):
+        return {'list': [_encode(x, arrays) for x in v]}
+    if isinstance(v, (bool, np.bool_)):
+        return {'bool': bool(v)}
+    if isinstance(v, (int, np.integer)):
+        return {'int': int(v)}
+    if isinstance(v, (float, np.floating)):
+        return {'float': float(v)}
+    if isinstance(v, str):
+        return {'str': str(v)}
+    raise TypeError('cannot record %r' % type(v))
+
+
+def _decode(e, arrays):
+    kind, v = next(iter(e.items()))
+    if kind == 'none':
+        return None
+    if kind == 'array':
+        return arrays[v]
+    if kind == 'digest':
+        return Digest(*v)
+    if kind == 'list':
+        return [_decode(x, arrays) for x in v]
+    return v
+
+
+def _call_key(name, attr, args=(), kwargs=None):
+    return json.dumps([name, attr, [str(a) for a in args], sorted((k, str(x)) for k, x in (kwargs or {}).items())])
+
+
+class _RecordedDatabase:
+    """one of the reference's database objects: live (every attribute read and call is logged) or played back from the log"""
+    def __init__(self, name, log, live=None):
+        self._name, self._log, self._live = name, log, live
+
+    def __getattr__(self, attr):
+        if attr.startswith('_'):
+            raise AttributeError(attr)
+        if self._live is None:
+            key = _call_key(self._name, '.' + attr)
+            if key in self._log:
+                return self._log[key]
+            return lambda *a, **k: self._log[_call_key(self._name, attr, a, k)]
+        v = getattr(self._live, attr)
+        if not callable(v):
+            self._log[_call_key(self._name, '.' + attr)] = v
+            return v
+
+        def call(*a, **k):
+            self._log[_call_key(self._name, attr, a, k)] = r = v(*a, **k)
+            return r
+        return call
+
+
+class _RecordedReference:
+    """the two entry points of the reference's dataset.database the tests call"""
+    def __init__(self, log, live=None):
+        self._log, self._live = log, live
+
+    def parse_database_name(self, name):
+        return _RecordedDatabase(name, self._log, self._live.parse_database_name(name) if self._live else None)
+
+    def get_database_split(self, db, split):
+        key = _call_key(db._name, 'get_database_split', (split,))
+        if self._live is None:
+            return self._log[key]
+        self._log[key] = r = self._live.get_database_split(db._live, split)
+        return r
+
+
 @pytest.fixture(scope='module')
 def ref_db(scenes):
-    """the reference's dataset.database with its roots pointed at the fixture and imread at PIL"""
-    if not ref_harness.reference_available():
-        pytest.skip('reference tree not present')
+    """the reference's dataset.database reading the fixture's files, as recorded in tests/golden/case_database_reference.npz: every
+    value the tests below read from it (small arrays stored, large ones as shape + dtype + sha256).  To re-record from a reference
+    checkout: NEURAY_RECORD_REFERENCE_DB=1 python -m pytest tests/test_database.py (the whole module), which runs the reference's
+    module with its roots pointed at the fixture, imread at PIL and its cv2 calls on the numpy restatements (tests/cv2_shim.py)."""
+    if not os.environ.get('NEURAY_RECORD_REFERENCE_DB'):
+        z = np.load(REF_DB_GOLDEN, allow_pickle=False)
+        arrays = {k: z[k] for k in z.files if k != 'index_json'}
+        log = {k: _decode(e, arrays) for k, e in json.loads(str(z['index_json'])).items()}
+        yield _RecordedReference(log)
+        return
+    assert ref_harness.reference_available(), 'recording needs the reference tree (NEURAY_REFERENCE_ROOT)'
     ref_harness.import_reference()
     import importlib
     mod = importlib.import_module('dataset.database')
@@ -139,16 +239,21 @@ def ref_db(scenes):
     mod.LLFF_ROOT = os.path.join(scenes['root'], 'llff_colmap')
     mod.imread = D.imread
     mod.imsave = D.imsave
-    # the reference's cv2 calls (resize / GaussianBlur / decomposeProjectionMatrix) run on the numpy restatements (tests/cv2_shim.py)
     import cv2_shim
     bu = importlib.import_module('utils.base_utils')
     mod.cv2 = bu.cv2 = cv2_shim
-    return mod
+    log = {}
+    yield _RecordedReference(log, mod)
+    arrays = {}
+    index = {k: _encode(v, arrays) for k, v in sorted(log.items())}
+    np.savez_compressed(REF_DB_GOLDEN, index_json=np.array(json.dumps(index, sort_keys=True)), **arrays)
 
 
 def same(a, b):
     if a is None or b is None:
         return a is None and b is None
+    if isinstance(b, Digest):
+        return b.matches(a)
     a, b = np.asarray(a), np.asarray(b)
     return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b)
 
