@@ -410,6 +410,23 @@ int neuray_direct_render_points(const float* query_const_dev, const float* view_
                                 int rfn, int rn, int dn, int h, int w, float ground, float* alpha_dev, float* color_dev, void* stream);
 int neuray_direct_render_rays(const float* alpha_dev, const float* colors_dev, int color_stride, int color_first, int rn, int dn,
                               float* hit_prob_dev, float* pixel_dev, void* stream);
+/* ---- backward of a18 (cfg['use_dr_loss'] / ['use_dr_fine_loss'], network/loss.py:70-76): autograd of renderer.py:85-125
+ * (predict_alpha_values_dr, predict_colors_dr, direct_rendering), sph_solver.py:33-59 and dist_decoder.py:109-144 for the SH colours
+ * (not use_nr_color_for_dr).  Not in the bf16-operand build.
+ * neuray_direct_render_rays_backward, per ray (render_ops.py:72-80, dist_decoder.py:142-144, renderer.py:124): alpha_dev [rn*dn] and
+ * colors_dev [rn*dn][3] are neuray_direct_render_points' outputs, d_pixel_dev [rn][3] and d_hit_prob_dev [rn][dn] (NULL = none) the
+ * gradients of pixel_colors_dr / hit_prob_dr -> d_alpha_dev [rn*dn] (of the logits alpha_dr), d_colors_dev [rn*dn][3].
+ * neuray_direct_render_points_backward, per sample point (renderer.py:85-111, sph_solver.py:33-59, dist_decoder.py:109-140): the inputs
+ * of neuray_direct_render_points (view_rec_dev: fields 0-11 are read), d_alpha_dev [rn*dn] / d_colors_dev [rn*dn][3] (either NULL = no
+ * gradient) -> d_dec_dev [rn*dn][rfn][6] = gradients of the pass decoder's outputs (mu0, mu1, s0, s1, aw, vis_dec) at every (point,
+ * view), zero rows where the view is masked; the vis_dec column is 0 unless use_vis (the COARSE decoder's cfg['use_vis'] and a vis head
+ * on this pass's decoder).  The colours C_v are image samples and take no gradient.  rfn <= NEURAY_MAX_VIEWS. */
+int neuray_direct_render_rays_backward(const float* alpha_dev, const float* colors_dev, const float* d_pixel_dev, const float* d_hit_prob_dev,
+                                       int rn, int dn, float* d_alpha_dev, float* d_colors_dev, void* stream);
+int neuray_direct_render_points_backward(const float* query_const_dev, const float* view_const_dev, const float* coords_dev,
+                                         const float* depth_dev, const float* rgba_dev, const float* view_rec_dev, const float* regs_dev,
+                                         const float* d_alpha_dev, const float* d_colors_dev, int rfn, int rn, int dn, int h, int w,
+                                         int use_vis, float* d_dec_dev, void* stream);
 
 /* ---- f-1 encoders: fused InstanceNorm2d(affine=True, eps) + activation (+ residual add) + reflection padding, NCHW fp32
  * (network/ops.py:43-75,150-230 ResidualBlock / ResUNetLight: `conv -> norm -> relu [-> + skip -> relu]`, `conv -> norm -> elu`;

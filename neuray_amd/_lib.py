@@ -124,6 +124,8 @@ SYMBOLS = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'neuray_direct_render_points': (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     'neuray_direct_render_rays': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'neuray_direct_render_rays_backward': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p] * 3),
+    'neuray_direct_render_points_backward': (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 6 + [C.c_void_p] * 2),
     'neuray_dist_decoder_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
     'neuray_self_hit_prob': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

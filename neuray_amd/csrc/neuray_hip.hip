@@ -3,7 +3,6 @@
 // CPU test emulator, g++ -DNEURAY_EMU (tests/emu/build_emu.py).
 #include "nr_kernels.h"
 #include "nr_kernels_bwd.h"
-#include "nr_kernels_dr.h"
 #include "nr_kernels_norm.h"
 #include "nr_kernels_conv3d.h"
 #include "nr_kernels_conv2d.h"
@@ -14,6 +13,7 @@
 #else
 #include "nr_kernels_bwd2.h"
 #endif
+#include "nr_kernels_dr.h"          // (after the NR_INFERENCE_ONLY decision: its backward half is training only)
 #include "nr_pack.h"
 #include "../../include/neuray_hip.h"
 
@@ -668,6 +668,40 @@ int neuray_direct_render_rays(const float* alpha, const float* colors, int color
     const int grid = grid_for(rn, 64, 256 * 8);
     NR_LAUNCH(nr::dr_rays_kernel, dim3(grid), dim3(64), 0, stream, alpha, colors, color_stride, color_first, rn, dn, hit_prob, pixel);
     return check_launch("neuray_direct_render_rays");
+}
+
+int neuray_direct_render_rays_backward(const float* alpha, const float* colors, const float* d_pixel, const float* d_hit_prob, int rn, int dn,
+                                       float* d_alpha, float* d_colors, void* stream) {
+#ifdef NR_INFERENCE_ONLY
+    (void)alpha; (void)colors; (void)d_pixel; (void)d_hit_prob; (void)rn; (void)dn; (void)d_alpha; (void)d_colors; (void)stream;
+    return fail("neuray_direct_render_rays_backward: the bf16-operand library is inference only");
+#else
+    if (rn < 1 || dn < 1) return fail("neuray_direct_render_rays_backward: bad shape rn=%d dn=%d", rn, dn);
+    if (!alpha || !colors || !d_pixel || !d_alpha || !d_colors) return fail("neuray_direct_render_rays_backward: missing array");
+    const int grid = grid_for(rn, 64, 256 * 8);
+    NR_LAUNCH(nr::dr_rays_backward_kernel, dim3(grid), dim3(64), 0, stream, alpha, colors, d_pixel, d_hit_prob, rn, dn, d_alpha, d_colors);
+    return check_launch("neuray_direct_render_rays_backward");
+#endif
+}
+
+int neuray_direct_render_points_backward(const float* query_const, const float* view_const, const float* coords, const float* depth,
+                                         const float* rgba, const float* view_rec, const float* regs, const float* d_alpha,
+                                         const float* d_colors, int rfn, int rn, int dn, int h, int w, int use_vis, float* d_dec,
+                                         void* stream) {
+#ifdef NR_INFERENCE_ONLY
+    (void)query_const; (void)view_const; (void)coords; (void)depth; (void)rgba; (void)view_rec; (void)regs; (void)d_alpha; (void)d_colors;
+    (void)rfn; (void)rn; (void)dn; (void)h; (void)w; (void)use_vis; (void)d_dec; (void)stream;
+    return fail("neuray_direct_render_points_backward: the bf16-operand library is inference only");
+#else
+    if (rfn < 1 || rfn > NEURAY_MAX_VIEWS || rn < 1 || dn < 1 || h < 1 || w < 1)
+        return fail("neuray_direct_render_points_backward: bad shape rfn=%d rn=%d dn=%d h=%d w=%d", rfn, rn, dn, h, w);
+    if (!query_const || !view_const || !coords || !depth || !rgba || !view_rec || !regs || !d_dec)
+        return fail("neuray_direct_render_points_backward: missing array");
+    const int grid = grid_for((long long)rn * dn, 128, 256 * 16);
+    NR_LAUNCH(nr::dr_points_backward_kernel, dim3(grid), dim3(128), 0, stream, query_const, view_const, coords, depth, rgba, view_rec, regs,
+              d_alpha, d_colors, rfn, rn, dn, h, w, use_vis, d_dec);
+    return check_launch("neuray_direct_render_points_backward");
+#endif
 }
 
 int neuray_dist_decoder_rows(const float* feats, const float* packed_weights, int n, int has_vis_head, float var_bias,

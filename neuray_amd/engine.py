@@ -871,6 +871,59 @@ class RenderEngine:
                                                        pix.data_ptr(), s))
         return {'hit_prob': hit, 'pixel': pix, 'alpha': alpha, 'colors': colors}
 
+    def direct_render_rays_backward(self, alpha, colors, d_pixel, d_hit_prob=None):
+        """Backward of direct_render's ray kernel: alpha [rn,dn] (logits), colors [rn,dn,3] (the SH colours), d_pixel [rn,3], d_hit_prob
+        [rn,dn] or None -> (d_alpha [rn,dn], d_colors [rn,dn,3])"""
+        alpha, colors, d_pixel = self._f32(alpha), self._f32(colors), self._f32(d_pixel)
+        rn, dn = alpha.shape
+        assert colors.numel() == rn * dn * 3 and d_pixel.shape == (rn, 3)
+        dh = self._f32(d_hit_prob) if d_hit_prob is not None else None
+        d_alpha, d_colors = self.empty(rn, dn), self.empty(rn, dn, 3)
+        self._check(self.lib.neuray_direct_render_rays_backward(alpha.data_ptr(), colors.data_ptr(), d_pixel.data_ptr(),
+                                                                dh.data_ptr() if dh is not None else None, rn, dn, d_alpha.data_ptr(),
+                                                                d_colors.data_ptr(), self._stream()))
+        return d_alpha, d_colors
+
+    def direct_render_points_backward(self, qconst, views, coords, depth, view_rec, regs, d_alpha, d_colors, use_vis):
+        """Backward of direct_render's point kernel -> d_dec [rn,dn,rfn,6]: gradients of the pass decoder's outputs (mu0, mu1, s0, s1,
+        aw, vis_dec) at every (point, view), zero where the view is masked.  use_vis: the coarse decoder's cfg['use_vis'] and a vis head
+        on this pass's decoder."""
+        coords, depth = self._f32(coords), self._f32(depth)
+        rn, dn = depth.shape
+        view_rec, regs = self._f32(view_rec), self._f32(regs.to(self.device))
+        assert view_rec.numel() == rn * dn * views.rfn * _lib.DBG_FIELDS and regs.numel() == 16
+        d_alpha = self._f32(d_alpha) if d_alpha is not None else None
+        d_colors = self._f32(d_colors) if d_colors is not None else None
+        d_dec = self.empty(rn, dn, views.rfn, 6)
+        self._check(self.lib.neuray_direct_render_points_backward(
+            qconst.data_ptr(), views.view_const.data_ptr(), coords.data_ptr(), depth.data_ptr(), views.rgba.data_ptr(), view_rec.data_ptr(),
+            regs.data_ptr(), d_alpha.data_ptr() if d_alpha is not None else None, d_colors.data_ptr() if d_colors is not None else None,
+            views.rfn, rn, dn, views.h, views.w, int(bool(use_vis)), d_dec.data_ptr(), self._stream()))
+        return d_dec
+
+    def direct_render_backward(self, qconst, views, coords, depth, view_rec, regs, alpha, colors, d_pixel, d_hit_prob, ray_feats, flat,
+                               has_vis_head, use_vis, var_bias=0.05, packed=None):
+        """Backward of direct_render (SH colours) down to the pass's dist decoder and its input map: the two dr backward kernels, then
+        the decoder rows at the recorded (u, v) - interpolate_feats of ray_feats (NCHW [rfn,32,fh,fw], renderer.py:67-72 /
+        render_ops.py:54-70) - through dist_decoder_rows_backward, and interpolate_feats_backward with the mask.
+        -> (d_ray_feats [rfn,32,fh,fw], d_flat [flat pass floats]: only the dist decoder's tensors are non-zero)"""
+        rn, dn = depth.shape
+        rfn = views.rfn
+        d_alpha, d_colors = self.direct_render_rays_backward(alpha, colors, d_pixel, d_hit_prob)
+        d_dec = self.direct_render_points_backward(qconst, views, coords, depth, view_rec, regs, d_alpha, d_colors,
+                                                   bool(use_vis) and bool(has_vis_head))
+        rec = view_rec.view(rn * dn, rfn, _lib.DBG_FIELDS).transpose(0, 1)                  # [rfn, npts, fields]
+        pts = rec[..., 1:3].contiguous()
+        mask = rec[..., 0].contiguous()
+        feats = self.interpolate_feats(ray_feats, pts, views.h, views.w, align_corners=False, mask=mask)      # [rfn, npts, 32]
+        g = d_dec.view(rn * dn, rfn, 6).transpose(0, 1)
+        d_feats, d_flat = self.dist_decoder_rows_backward(
+            feats, flat, has_vis_head, var_bias, d_mean=g[..., 0:2].contiguous(), d_var=g[..., 2:4].contiguous(),
+            d_aw=g[..., 4].contiguous(), d_vis=g[..., 5].contiguous() if has_vis_head else None, packed=packed)
+        d_map = self.interpolate_feats_backward(d_feats.view(rfn, rn * dn, 32), tuple(ray_feats.shape), pts, views.h, views.w,
+                                                align_corners=False, mask=mask)
+        return d_map, d_flat
+
     def render_rays(self, point_rec, depth, packed, save=False, ray_mask_view_num=2, ray_mask_point_num=8):
         """The ray kernel alone on per-point records [rn,dn,POINT_REC]: -> dict(hit_prob, pixel, att_saved?)"""
         point_rec, depth = self._f32(point_rec), self._f32(depth)

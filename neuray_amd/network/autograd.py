@@ -1,5 +1,6 @@
 """torch.autograd glue of the HIP render path: the forward runs the forward kernels, the backward the backward kernels
 (include/neuray_hip.h: neuray_render_rays_backward, neuray_render_points_backward, neuray_self_hit_prob_backward,
+neuray_direct_render_rays_backward, neuray_direct_render_points_backward, neuray_dist_decoder_rows_backward,
 neuray_interpolate_feats_backward).  Nothing here computes with PyTorch ops besides layout permutes and slicing."""
 import torch
 
@@ -174,3 +175,38 @@ class SelfHitFn(torch.autograd.Function):
         d_map = eng.interpolate_feats_backward(d_feats[None], ctx.shape, run.coords[None], ctx.hw[0], ctx.hw[1], align_corners=False)
         grads = eng.unflatten_pass_grads(d_flat, sd, 'd.', 'a.')
         return (None, None, None, d_map) + tuple(grads[k] for k, _ in run.dist_params())
+
+
+class DirectRenderFn(torch.autograd.Function):
+    """(ray_feats NCHW, *run.dist_params()) -> pixel_colors_dr [rn,3], hit_prob_dr [rn,dn]: direct rendering with the SH colours
+    (renderer.py:85-125, sph_solver.py) as a function of the pass decoder's weights and the reference views' ray_feats, for
+    cfg['use_dr_loss'] / ['use_dr_fine_loss'] (loss.py:70-76).  The forward reruns the point kernel for its per-view record (the pass
+    itself runs as RenderPassFn without it) and the dr kernels; it keeps the record (64 B per sample point and view: 16 MB per pass at
+    512 rays x 64 samples x 8 views), the alpha logits and the colours until the backward, which runs the dr backward kernels, the dist
+    decoder's row backward and the feature map's interpolation backward (engine.direct_render_backward).  Autograd adds these gradients
+    to RenderPassFn's for the same tensors."""
+
+    @staticmethod
+    def forward(ctx, run, regs, ground, ray_feats, *params):
+        eng = run.eng
+        flat, packed, has_vis = run.device_weights()
+        res = eng.render_pass(run.qconst, run.views, run.coords, run.depth, packed, use_vis=run.use_vis, var_bias=run.var_bias,
+                              want_dbg=True)
+        dr = eng.direct_render(run.qconst, run.views, run.coords, run.depth, res['dbg'], regs, ground=ground)
+        ctx.run, ctx.regs, ctx.flat, ctx.packed, ctx.has_vis = run, regs, flat, packed, has_vis
+        ctx.save_for_backward(ray_feats, res['dbg'], dr['alpha'], dr['colors'])
+        return dr['pixel'], dr['hit_prob']
+
+    @staticmethod
+    def backward(ctx, d_pixel, d_hit):
+        run, eng = ctx.run, ctx.run.eng
+        ray_feats, rec, alpha, colors = ctx.saved_tensors
+        rn, dn = run.depth.shape
+        if d_pixel is None:
+            d_pixel = torch.zeros(rn, 3, device=alpha.device)
+        d_map, d_flat = eng.direct_render_backward(run.qconst, run.views, run.coords, run.depth, rec, ctx.regs, alpha, colors,
+                                                   d_pixel.contiguous(), d_hit.contiguous() if d_hit is not None else None,
+                                                   ray_feats.detach(), ctx.flat, ctx.has_vis, run.use_vis, var_bias=run.var_bias,
+                                                   packed=ctx.packed)
+        grads = eng.unflatten_pass_grads(d_flat, run.state(), 'd.', 'a.')
+        return (None, None, None, d_map if ctx.needs_input_grad[3] else None) + tuple(grads[k] for k, _ in run.dist_params())

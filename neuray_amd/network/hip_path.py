@@ -15,7 +15,7 @@ import os
 import torch
 
 from ..engine import RenderEngine
-from .autograd import PassRun, RenderPassFn, RenderPassSelfFn, SelfHitFn
+from .autograd import DirectRenderFn, PassRun, RenderPassFn, RenderPassSelfFn, SelfHitFn
 
 HOT_PATH_METHODS = ('engine', '_packed_pass', '_same_tensors', '_views', '_query', '_self_hit_prob', '_direct_rendering',
                     'render_by_depth', 'predict_self_hit_prob', 'fine_render_impl', 'render_impl')
@@ -115,7 +115,7 @@ class HipRenderPath:
                                   want_depth=cfg['render_depth'], want_dbg=bool(cfg.get('use_dr_prediction', False)))
         outputs = {'pixel_colors_nr': res['pixel'][None], 'hit_prob_nr': res['hit_prob'][None]}
         if cfg.get('use_dr_prediction', False):           # renderer.py:181-185
-            outputs.update(self._direct_rendering(eng, qconst, views, run, res, packed, is_fine))
+            outputs.update(self._direct_rendering(eng, qconst, views, run, res, packed, is_fine, ref_imgs_info['ray_feats']))
         if is_train and cfg['use_self_hit_prob']:
             outputs['hit_prob_self'] = res['hit_self'][None] if res.get('hit_self') is not None else \
                 self._self_hit_prob(que_imgs_info, que_depth, is_fine, run, packed)
@@ -127,21 +127,30 @@ class HipRenderPath:
             outputs['render_depth'] = res['render_depth'][None]
         return outputs
 
-    def _direct_rendering(self, eng, qconst, views, run, res, packed, is_fine):
+    def _direct_rendering(self, eng, qconst, views, run, res, packed, is_fine, ray_feats=None):
         """renderer.py:85-125 (+ sph_solver.py) on the dr kernels -> {'pixel_colors_dr', 'hit_prob_dr'}.  The per-view hit
         probabilities / visibilities come from the point kernel's per-view record; under autograd the pass itself ran as an
-        autograd.Function without that record, so the point kernel is run once more for it, and the dr outputs are returned
-        DETACHED: the backward kernels cover the losses of every shipped config (loss.py use_dr_loss: false everywhere)."""
+        autograd.Function without that record, so the point kernel is run once more for it.  With a dr loss (cfg use_dr_loss /
+        use_dr_fine_loss, loss.py:70-76) the outputs of both passes carry gradients into the pass's dist decoder and ray_feats
+        (autograd.DirectRenderFn); without one they are returned DETACHED (use_dr_prediction alone is a prediction)."""
         cfg = self.cfg
         rec = res.get('dbg')
         point_rec = res.get('point_rec')
+        fitter = getattr(self, 'sph_fitter', None)
+        regs = fitter.regs if fitter is not None and hasattr(fitter, 'regs') else \
+            torch.tensor([0.0] + [0.001] * 3 + [0.005] * 5 + [0.05] * 7, dtype=torch.float32)       # sph_solver.py:6-12, degree 3
         if rec is None:
             if cfg.get('use_dr_loss') or cfg.get('use_dr_fine_loss'):
-                # the reference back-propagates those losses through direct_rendering (loss.py: RenderLoss reads pixel_colors_dr); the
-                # backward kernels do not, and a loss term that silently contributes no gradient is worse than an error
-                raise NotImplementedError("neuray_amd: cfg use_dr_loss / use_dr_fine_loss need gradients through direct_rendering "
-                                          "(renderer.py:85-125), which the HIP backward kernels do not provide; the prediction-only "
-                                          "use_dr_prediction (no dr loss) is supported")
+                if cfg.get('use_nr_color_for_dr', False):
+                    # the dr colours would be the aggregation network's (RenderPassFn's point records): their gradient would have to reach
+                    # the aggregation network through the pass's own backward, which the HIP path does not route
+                    raise NotImplementedError("neuray_amd: cfg use_nr_color_for_dr together with use_dr_loss / use_dr_fine_loss needs "
+                                              "gradients from direct_rendering (renderer.py:113-125) into the aggregation network, which "
+                                              "the HIP path does not provide; the dr losses train with the spherical-harmonics colours "
+                                              "(use_nr_color_for_dr: false)")
+                pix, hitp = DirectRenderFn.apply(run, regs, float(cfg['alpha_value_ground_state']), ray_feats,
+                                                 *[p for _, p in run.dist_params()])
+                return {'pixel_colors_dr': pix[None], 'hit_prob_dr': hitp[None]}
             if not self.__dict__.get('_dr_grad_warned'):
                 import warnings
                 warnings.warn("neuray_amd: use_dr_prediction under autograd - pixel_colors_dr / hit_prob_dr are computed but carry "
@@ -152,9 +161,6 @@ class HipRenderPath:
                 again = eng.render_pass(qconst, views, run.coords, run.depth, packed, use_vis=run.use_vis, var_bias=run.var_bias,
                                         want_dbg=True)
             rec, point_rec = again['dbg'], again['point_rec']
-        fitter = getattr(self, 'sph_fitter', None)
-        regs = fitter.regs if fitter is not None and hasattr(fitter, 'regs') else \
-            torch.tensor([0.0] + [0.001] * 3 + [0.005] * 5 + [0.05] * 7, dtype=torch.float32)       # sph_solver.py:6-12, degree 3
         with torch.no_grad():
             dr = eng.direct_render(qconst, views, run.coords, run.depth, rec, regs, ground=float(cfg['alpha_value_ground_state']),
                                    point_rec=point_rec if cfg.get('use_nr_color_for_dr', False) else None)
