@@ -479,6 +479,33 @@ int neuray_self_hit_prob(const float* query_const_dev, const float* depth_dev, c
  * interpreter lock (the host side of neuray_amd draws the NEXT step's rays on a worker thread while the current step is queued). */
 int neuray_mt19937_shuffle(unsigned int* key624_host, int* pos_host, void* data_host, long long n, int itemsize);
 
+/* ---- image metrics: network/metrics.py (PSNR_SSIM / compute_psnr / VisualizeImage: validation and checkpoint selection,
+ * val_metric [psnr_ssim, vis_img], key_metric_name psnr_nr_fine) and eval.py (tf.image.ssim) - for n image pairs of one size h x w x 3.
+ *   pred_dev: fp32 [n][h*w][3] (rendered colours, quantised on load exactly as utils/base_utils.py:496-499 color_map_backward:
+ *             clip(x * 255f, 0, 255) truncated, NaN -> 0) or, with input_u8, uint8 [n][h][w][3] (decoded image files)
+ *   gt_dev: the same type; pair i compares pred image i with gt image i * gt_stride (0: one ground truth for every prediction)
+ *   quant_dev (NULL = none): uint8 [n][h][w][3] <- the quantised predictions (the ROI's pixels; the rest is not written)
+ *   roi_y0 .. roi_y1, roi_x0 .. roi_x1 (half-open): the measured crop (PSNR_SSIM's eval_margin_ratio); at least 11 x 11, else an error
+ * -> sse_dev [n]: sum of squared uint8 differences over the ROI (exact; PSNR = 10 log10(255^2 * 3 N / SSE), N = ROI pixels)
+ *    ssim_dev [n]: mean over the valid 11 x 11 window positions inside the ROI, averaged over the three channels, K1 = 0.01,
+ *    K2 = 0.03, data range 255.  variant NEURAY_SSIM_BOX11: skimage structural_similarity(win_size=11, data_range=255) - uniform
+ *    window, sample covariance; NEURAY_SSIM_GAUSS11: tf.image.ssim - Gaussian window (sigma 1.5), biased moments.  fp64, fixed
+ *    reduction order: a pair's values do not depend on the rest of the batch.
+ * workspace_dev: neuray_image_metrics_workspace_bytes(n, h, w) bytes (-1: a shape no call accepts).  Two launches, no synchronisation. */
+#define NEURAY_SSIM_BOX11 0
+#define NEURAY_SSIM_GAUSS11 1
+typedef struct NeurayImageMetricsArgs {
+    const void* pred_dev;
+    const void* gt_dev;
+    unsigned char* quant_dev;
+    unsigned long long* sse_dev;
+    double* ssim_dev;
+    void* workspace_dev;
+    int n, gt_stride, input_u8, h, w, roi_y0, roi_y1, roi_x0, roi_x1, variant;
+} NeurayImageMetricsArgs;
+long long neuray_image_metrics_workspace_bytes(int n, int h, int w);
+int neuray_image_metrics(const NeurayImageMetricsArgs* args, void* stream);
+
 /* ---- hardware self test of the MFMA operand layout the kernels assume (16x4 @ 4x16) ----------------------------- */
 int neuray_mfma_selftest(const float* A_dev, const float* B_dev, float* D_dev, void* stream);
 /* ---- hardware self test of the lane-group sum behind the vector rows (v_permlane16_swap / v_permlane32_swap):

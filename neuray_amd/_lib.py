@@ -72,6 +72,13 @@ class NeurayPointsBwdArgs(C.Structure):
          ('handover_dev', C.c_void_p)]
 
 
+class NeurayImageMetricsArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('pred_dev', 'gt_dev', 'quant_dev', 'sse_dev', 'ssim_dev', 'workspace_dev')] + \
+        [(n, C.c_int) for n in ('n', 'gt_stride', 'input_u8', 'h', 'w', 'roi_y0', 'roi_y1', 'roi_x0', 'roi_x1', 'variant')]
+
+
+SSIM_BOX11, SSIM_GAUSS11 = 0, 1   # NeurayImageMetricsArgs.variant (include/neuray_hip.h NEURAY_SSIM_*)
+
 PACKED_RAY_FLOATS = 1348
 RAY_ATT_SAVE = 24            # NEURAY_RAY_ATT_SAVE
 # (state_dict suffix under agg_net.agg_impl., offset, shape) of the ray-part weights inside d_ray_weights (include/neuray_hip.h)
@@ -168,6 +175,8 @@ SYMBOLS = {
     'neuray_conv3d_c8_c1': (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'neuray_convtranspose3d_c16_c8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'neuray_diff_feats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'neuray_image_metrics_workspace_bytes': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    'neuray_image_metrics': (C.c_int, [C.POINTER(NeurayImageMetricsArgs), C.c_void_p]),
 }
 
 

@@ -6,6 +6,7 @@
 #include "nr_kernels_norm.h"
 #include "nr_kernels_conv3d.h"
 #include "nr_kernels_conv2d.h"
+#include "nr_kernels_metrics.h"
 // the plain bf16-operand build is inference only; the fp32 build and the split build (hi + lo bf16 operands: fp32-grade products)
 // carry the training path
 #if defined(NR_BF16_QUADS) && !defined(NR_BF16_SPLIT)
@@ -17,6 +18,7 @@
 #include "nr_pack.h"
 #include "../../include/neuray_hip.h"
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -924,6 +926,56 @@ int neuray_interpolate_feats_backward_staged(const float* d_out, const float* po
 int neuray_group_sum_selftest(const float* x, float* y, void* stream) {
     NR_LAUNCH(nr::group_sum_selftest_kernel, dim3(1), dim3(64), 0, stream, x, y);
     return check_launch("neuray_group_sum_selftest");
+}
+
+// ---- image metrics (nr_kernels_metrics.h) -------------------------------------------------------------------------------------------
+static void metrics_tiles(int y0, int y1, int x0, int x1, int& tiles_y, int& tiles_x) {
+    tiles_y = (y1 - y0 - (nr::kMetWin - 1) + nr::kMetTH - 1) / nr::kMetTH;
+    tiles_x = (x1 - x0 - (nr::kMetWin - 1) + nr::kMetTW - 1) / nr::kMetTW;
+}
+
+long long neuray_image_metrics_workspace_bytes(int n, int h, int w) {
+    if (n < 1 || h < nr::kMetWin || w < nr::kMetWin) return -1;
+    int ty, tx;
+    metrics_tiles(0, h, 0, w, ty, tx);           // (a smaller ROI has fewer tiles)
+    return (long long)n * ty * tx * nr::kMetPartial * 8;
+}
+
+int neuray_image_metrics(const NeurayImageMetricsArgs* a, void* stream) {
+    if (!a) return fail("neuray_image_metrics: null args");
+    if (!a->pred_dev || !a->gt_dev || !a->sse_dev || !a->ssim_dev || !a->workspace_dev) return fail("neuray_image_metrics: missing array");
+    if (a->n < 1 || a->h < 1 || a->w < 1 || a->gt_stride < 0) return fail("neuray_image_metrics: bad shape n=%d h=%d w=%d gt_stride=%d", a->n, a->h, a->w, a->gt_stride);
+    if (a->variant != NEURAY_SSIM_BOX11 && a->variant != NEURAY_SSIM_GAUSS11) return fail("neuray_image_metrics: unknown SSIM variant %d", a->variant);
+    if (a->roi_y0 < 0 || a->roi_x0 < 0 || a->roi_y1 > a->h || a->roi_x1 > a->w || a->roi_y0 >= a->roi_y1 || a->roi_x0 >= a->roi_x1)
+        return fail("neuray_image_metrics: region [%d, %d) x [%d, %d) is not inside the %d x %d image", a->roi_y0, a->roi_y1, a->roi_x0, a->roi_x1, a->h, a->w);
+    if (a->roi_y1 - a->roi_y0 < nr::kMetWin || a->roi_x1 - a->roi_x0 < nr::kMetWin)
+        return fail("neuray_image_metrics: the %d x %d region is smaller than the 11 x 11 SSIM window", a->roi_y1 - a->roi_y0, a->roi_x1 - a->roi_x0);
+    nr::MetricsParams p;
+    p.pred = a->pred_dev; p.gt = a->gt_dev; p.quant = a->quant_dev; p.sse = a->sse_dev; p.ssim = a->ssim_dev;
+    p.ws = static_cast<double*>(a->workspace_dev);
+    p.n = a->n; p.gt_stride = a->gt_stride; p.u8 = a->input_u8 ? 1 : 0; p.h = a->h; p.w = a->w;
+    p.y0 = a->roi_y0; p.y1 = a->roi_y1; p.x0 = a->roi_x0; p.x1 = a->roi_x1;
+    metrics_tiles(p.y0, p.y1, p.x0, p.x1, p.tiles_y, p.tiles_x);
+    // tf.image.ssim's window (_fspecial_gauss: softmax of -0.5 (i^2 + j^2) / 1.5^2) is the outer product of this normalised 1-D one
+    double sum = 0.0;
+    for (int k = 0; k < nr::kMetWin; ++k) {
+        const double d = k - (nr::kMetWin - 1) / 2;
+        p.taps[k] = std::exp(-0.5 * d * d / (1.5 * 1.5));
+        sum += p.taps[k];
+    }
+    for (int k = 0; k < nr::kMetWin; ++k) p.taps[k] /= sum;
+    const long long blocks = (long long)p.n * p.tiles_y * p.tiles_x;
+    if (blocks > 0x7fffffffLL) return fail("neuray_image_metrics: %lld tiles", blocks);
+    const bool gauss = a->variant == NEURAY_SSIM_GAUSS11;
+    auto k = gauss ? nr::image_metrics_tile_kernel<true> : nr::image_metrics_tile_kernel<false>;
+    const size_t smem = gauss ? nr::metrics_smem_bytes<true>() : nr::metrics_smem_bytes<false>();     // 86 304 / 53 024 bytes
+#ifndef NEURAY_EMU
+    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+#endif
+    NR_LAUNCH(k, dim3((unsigned)blocks), dim3(nr::kMetThreads), smem, stream, p);
+    if (int rc = check_launch("neuray_image_metrics")) return rc;
+    NR_LAUNCH(nr::image_metrics_reduce_kernel, dim3(p.n), dim3(64), 4 * 64 * 8, stream, p);
+    return check_launch("neuray_image_metrics");
 }
 
 #ifdef NR_B2_PROFILE

@@ -955,3 +955,39 @@ class RenderEngine:
             int(packed.has_vis_head), int(bool(use_vis)), float(var_bias), 0, saved.data_ptr(), 0, None, _lib.ARITH_F32)
         self._check(self.lib.neuray_render_points(C.byref(a), self._stream()))
         return saved
+
+    def image_metrics(self, pred, gt, h, w, ssim='box11', roi=None, quantised_out=None):
+        """PSNR / SSIM of n image pairs of one size (neuray_image_metrics; network/metrics.py, eval.py).  pred: float32 [n, h*w, 3]
+        (rendered colours, quantised like color_map_backward) or uint8 [n, h, w, 3]; gt: the same dtype, batch 1 (compared with every
+        prediction, read once per tile) or n.  ssim: 'box11' (skimage structural_similarity, the validation metric) or 'gauss11'
+        (tf.image.ssim, eval.py).  roi: (y0, y1, x0, x1), half-open, at least 11 x 11 (default: the whole image).  quantised_out:
+        optional uint8 [n, h, w, 3] device tensor <- the quantised predictions inside the ROI.
+        -> dict of device tensors: sse int64 [n], ssim float64 [n], psnr float64 [n] (inf where sse == 0)"""
+        variant = {'box11': _lib.SSIM_BOX11, 'gauss11': _lib.SSIM_GAUSS11}.get(ssim)
+        if variant is None:
+            raise ValueError("neuray_amd: ssim=%r (use 'box11' or 'gauss11')" % (ssim,))
+        if pred.dtype not in (torch.float32, torch.uint8) or gt.dtype != pred.dtype:
+            raise TypeError("neuray_amd.image_metrics: pred and gt must both be float32 or both uint8 (got %s, %s)" % (pred.dtype, gt.dtype))
+        h, w = int(h), int(w)
+        pred = pred.detach().to(self.device).contiguous()
+        gt = gt.detach().to(self.device).contiguous()
+        img = h * w * 3
+        n = pred.numel() // img if img > 0 else 0
+        if n < 1 or pred.numel() != n * img or gt.numel() not in (img, n * img):
+            raise ValueError("neuray_amd.image_metrics: pred %s / gt %s are not n (resp. 1 or n) images of %d x %d x 3"
+                             % (tuple(pred.shape), tuple(gt.shape), h, w))
+        y0, y1, x0, x1 = (0, h, 0, w) if roi is None else (int(v) for v in roi)
+        if quantised_out is not None:
+            if (quantised_out.dtype != torch.uint8 or quantised_out.numel() != n * img or not quantised_out.is_contiguous()
+                    or quantised_out.device != self.device):
+                raise ValueError("neuray_amd.image_metrics: quantised_out must be a contiguous uint8 [n, h, w, 3] tensor on %s" % self.device)
+        ws_bytes = int(self.lib.neuray_image_metrics_workspace_bytes(n, h, w))
+        ws = self.empty(max(ws_bytes, 8), dtype=torch.uint8)
+        sse, val = self.empty(n, dtype=torch.int64), self.empty(n, dtype=torch.float64)
+        a = _lib.NeurayImageMetricsArgs(pred.data_ptr(), gt.data_ptr(), quantised_out.data_ptr() if quantised_out is not None else None,
+                                        sse.data_ptr(), val.data_ptr(), ws.data_ptr(), n, 0 if gt.numel() == img else 1,
+                                        int(pred.dtype == torch.uint8), h, w, y0, y1, x0, x1, variant)
+        self._check(self.lib.neuray_image_metrics(C.byref(a), self._stream()))
+        pixels = (y1 - y0) * (x1 - x0)
+        psnr = torch.log10((255.0 * 255.0 * 3 * pixels) / sse.to(torch.float64)) * 10.0
+        return {'sse': sse, 'ssim': val, 'psnr': psnr}

@@ -26,6 +26,8 @@ Options swap the neighbouring per-image pieces too (each is the same arithmetic 
   ft_host=True      NeuralRayFtRenderer.slice_imgs_info (renderer.py:469-491) -> the resident-scene host path: the scene's views are
                     moved to the device once instead of `to_cuda(imgs_info_slice(...))` of 100 MB per step, the ray sampler works from
                     cached pixel lists (same np.random draws, same rays), no synchronous copy is left in a step
+  metrics=True      network.metrics (PSNR_SSIM, VisualizeImage, compute_psnr, structural_similarity, name2metrics, ...) -> neuray_amd.metrics:
+                    validation PSNR / SSIM on the HIP metrics kernels (the reference's module needs skimage)
 """
 import importlib
 import sys
@@ -60,7 +62,7 @@ def unpatch_renderer_class(cls):
             delattr(cls, name)
 
 
-def patch_reference(renderer_module=None, render_ops=False, init_nets=False, ft_host=False, render_loop=False):
+def patch_reference(renderer_module=None, render_ops=False, init_nets=False, ft_host=False, render_loop=False, metrics=False):
     """Patch the reference's `network.renderer` (imported here if it is not yet; the reference tree must be importable).
     -> the patched module."""
     mod = renderer_module if renderer_module is not None else (
@@ -85,7 +87,50 @@ def patch_reference(renderer_module=None, render_ops=False, init_nets=False, ft_
         ref_init = importlib.import_module('network.init_net')
         _PATCHED.setdefault(ref_init, {}).setdefault('get_diff_feats', ref_init.get_diff_feats)
         ref_init.get_diff_feats = hip_init.get_diff_feats
+    if metrics:
+        patch_metrics()
     return mod
+
+
+_METRICS = {}
+
+
+def patch_metrics():
+    """network.metrics -> neuray_amd.metrics: installed as sys.modules['network.metrics'] (and the `network` package's attribute)
+    before the reference's module is imported; if it already is, its public names are replaced in place.  Idempotent."""
+    from . import metrics as ours
+    if _METRICS:
+        return
+    ref = sys.modules.get('network.metrics')
+    if ref is not None and ref is not ours:
+        _METRICS['names'] = (ref, {name: getattr(ref, name) for name in ours.__all__ if hasattr(ref, name)})
+        for name in ours.__all__:
+            setattr(ref, name, getattr(ours, name))
+    else:
+        pkg = sys.modules.get('network')
+        _METRICS['module'] = (pkg, pkg.__dict__.get('metrics') if pkg is not None else None)
+        sys.modules['network.metrics'] = ours
+        if pkg is not None:
+            pkg.metrics = ours
+
+
+def unpatch_metrics():
+    if 'names' in _METRICS:
+        ref, saved = _METRICS.pop('names')
+        from . import metrics as ours
+        for name in ours.__all__:
+            if name in saved:
+                setattr(ref, name, saved[name])
+            else:
+                delattr(ref, name)
+    if 'module' in _METRICS:
+        pkg, attr = _METRICS.pop('module')
+        sys.modules.pop('network.metrics', None)
+        if pkg is not None:
+            if attr is None:
+                pkg.__dict__.pop('metrics', None)
+            else:
+                pkg.metrics = attr
 
 
 RENDER_LOOP_METHODS = ('render', 'encode_views', '_early_query')
@@ -157,6 +202,7 @@ def unpatch_ft_host(ft_cls):
 
 
 def unpatch_reference(renderer_module=None):
+    unpatch_metrics()
     mod = renderer_module if renderer_module is not None else sys.modules.get('network.renderer')
     if mod is not None:
         unpatch_renderer_class(mod.NeuralRayBaseRenderer)
