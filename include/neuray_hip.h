@@ -506,6 +506,51 @@ typedef struct NeurayImageMetricsArgs {
 long long neuray_image_metrics_workspace_bytes(int n, int h, int w);
 int neuray_image_metrics(const NeurayImageMetricsArgs* args, void* stream);
 
+/* ---- training losses: network/loss.py (RenderLoss 57-77, ConsistencyLoss 29-44, DepthLoss 91-132; cfg loss [render, depth] /
+ * [render, consist]) - one *loss call*: up to NEURAY_LOSS_MAX_TERMS terms of one loss object in one forward and one backward launch.
+ * A term reduces `rows` rows of `n` elements to one fp32 value per row (fp32 element arithmetic in the reference's order, fp64 sums in
+ * a fixed order: a term's value does not depend on the other terms of the call or on the run).
+ *   NEURAY_LOSS_RENDER   loss.py:57-77  pred_dev / ref_dev [rows][n][3] (pixel_colors_*, pixel_colors_gt), mask_dev [rows][n] or NULL
+ *                        (fp32, or one byte per ray with mask_u8): sum_c (pr - gt)^2, then sum(l m) / (sum(m) + 1e-3) or the mean
+ *   NEURAY_LOSS_CONSIST  loss.py:29-44  pred_dev p1 = hit_prob_self, ref_dev p0 = hit_prob_nr (a constant), both [rows][n], n = rn * inner:
+ *                        -p0 log(p1 + 1e-5) - (1 - p0) log(1 - p1 + 1e-5), the mean over inner (dn), then over rn
+ *   NEURAY_LOSS_DEPTH    loss.py:91-132 pred_dev depth_mean, element (row, i) at (row n + i) stride; ref_dev true_depth [rows][h][w];
+ *                        coords_dev [rows][n][2] (fp32, or int64 with coords_i64) used as (x, y); range_dev [rows][2] near / far;
+ *                        mask_dev the noisy depth map [rows][h][w] of a gso scene or NULL.  The bilinear read is interpolate_feats
+ *                        (padding_mode='border', align_corners=True), then process() (clamp 1e-5, -1 / d, normalise, clamp [0, 1]),
+ *                        (gt - pr)^2 or, with smooth_l1, SmoothL1(beta); gso: m = |aug - gt| < thresh, sum(l m) / (sum(m) + 1e-4), else the mean
+ * neuray_train_loss: value_dev [sum of rows] <- the terms' rows in table order, den_dev [sum of rows] <- the denominators (kept for the
+ *   backward); workspace_dev: neuray_train_loss_workspace_bytes(terms, n_terms) bytes (-1: a table no call accepts).  grad_out_dev and
+ *   d_pred_dev are not read.  Two launches, no synchronisation.
+ * neuray_train_loss_backward: the same table and den_dev; per term grad_out_dev [rows] (the upstream gradient of every row) and
+ *   d_pred_dev <- the gradient of pred ([rows][n][3] / [rows][n], contiguous; NULL: the term's prediction needs none).  The element-wise
+ *   derivative is recomputed from the inputs; ref, mask, maps, coordinates and ranges receive no gradient.  One launch. */
+#define NEURAY_LOSS_RENDER 0
+#define NEURAY_LOSS_CONSIST 1
+#define NEURAY_LOSS_DEPTH 2
+#define NEURAY_LOSS_MAX_TERMS 4
+typedef struct NeurayLossTerm {
+    const float* pred_dev;
+    const float* ref_dev;
+    const void* mask_dev;
+    const void* coords_dev;
+    const float* range_dev;
+    const float* grad_out_dev;
+    float* d_pred_dev;
+    int kind, rows, n, inner, stride, h, w, coords_i64, mask_u8, smooth_l1;
+    float beta, thresh;
+} NeurayLossTerm;
+typedef struct NeurayTrainLossArgs {
+    const NeurayLossTerm* terms;      /* host array of n_terms entries */
+    float* value_dev;
+    double* den_dev;
+    void* workspace_dev;
+    int n_terms, reserved;
+} NeurayTrainLossArgs;
+long long neuray_train_loss_workspace_bytes(const NeurayLossTerm* terms, int n_terms);
+int neuray_train_loss(const NeurayTrainLossArgs* args, void* stream);
+int neuray_train_loss_backward(const NeurayTrainLossArgs* args, void* stream);
+
 /* ---- hardware self test of the MFMA operand layout the kernels assume (16x4 @ 4x16) ----------------------------- */
 int neuray_mfma_selftest(const float* A_dev, const float* B_dev, float* D_dev, void* stream);
 /* ---- hardware self test of the lane-group sum behind the vector rows (v_permlane16_swap / v_permlane32_swap):

@@ -79,6 +79,21 @@ class NeurayImageMetricsArgs(C.Structure):
 
 SSIM_BOX11, SSIM_GAUSS11 = 0, 1   # NeurayImageMetricsArgs.variant (include/neuray_hip.h NEURAY_SSIM_*)
 
+
+
+class NeurayLossTerm(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('pred_dev', 'ref_dev', 'mask_dev', 'coords_dev', 'range_dev', 'grad_out_dev', 'd_pred_dev')] + \
+        [(n, C.c_int) for n in ('kind', 'rows', 'n', 'inner', 'stride', 'h', 'w', 'coords_i64', 'mask_u8', 'smooth_l1')] + \
+        [('beta', C.c_float), ('thresh', C.c_float)]
+
+
+class NeurayTrainLossArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('terms', 'value_dev', 'den_dev', 'workspace_dev')] + [('n_terms', C.c_int), ('reserved', C.c_int)]
+
+
+LOSS_RENDER, LOSS_CONSIST, LOSS_DEPTH = 0, 1, 2   # NeurayLossTerm.kind (include/neuray_hip.h NEURAY_LOSS_*)
+LOSS_MAX_TERMS = 4
+
 PACKED_RAY_FLOATS = 1348
 RAY_ATT_SAVE = 24            # NEURAY_RAY_ATT_SAVE
 # (state_dict suffix under agg_net.agg_impl., offset, shape) of the ray-part weights inside d_ray_weights (include/neuray_hip.h)
@@ -177,6 +192,9 @@ SYMBOLS = {
     'neuray_diff_feats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'neuray_image_metrics_workspace_bytes': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     'neuray_image_metrics': (C.c_int, [C.POINTER(NeurayImageMetricsArgs), C.c_void_p]),
+    'neuray_train_loss_workspace_bytes': (C.c_longlong, [C.POINTER(NeurayLossTerm), C.c_int]),
+    'neuray_train_loss': (C.c_int, [C.POINTER(NeurayTrainLossArgs), C.c_void_p]),
+    'neuray_train_loss_backward': (C.c_int, [C.POINTER(NeurayTrainLossArgs), C.c_void_p]),
 }
 
 

@@ -7,6 +7,7 @@
 #include "nr_kernels_conv3d.h"
 #include "nr_kernels_conv2d.h"
 #include "nr_kernels_metrics.h"
+#include "nr_kernels_loss.h"
 // the plain bf16-operand build is inference only; the fp32 build and the split build (hi + lo bf16 operands: fp32-grade products)
 // carry the training path
 #if defined(NR_BF16_QUADS) && !defined(NR_BF16_SPLIT)
@@ -976,6 +977,76 @@ int neuray_image_metrics(const NeurayImageMetricsArgs* a, void* stream) {
     if (int rc = check_launch("neuray_image_metrics")) return rc;
     NR_LAUNCH(nr::image_metrics_reduce_kernel, dim3(p.n), dim3(64), 4 * 64 * 8, stream, p);
     return check_launch("neuray_image_metrics");
+}
+
+// ---- training losses (nr_kernels_loss.h) --------------------------------------------------------------------------------------------
+// term table of the ABI -> the kernels' (chunks, first workgroup and first row of every term); 0 or the error already recorded
+static int loss_params(const char* what, const NeurayLossTerm* terms, int n_terms, bool backward, nr::LossParams& p, long long& blocks) {
+    if (!terms) return fail("%s: null term table", what);
+    if (n_terms < 1 || n_terms > nr::kLossMaxTerms) return fail("%s: %d terms (1 .. %d)", what, n_terms, nr::kLossMaxTerms);
+    blocks = 0;
+    int rows = 0;
+    for (int i = 0; i < n_terms; ++i) {
+        const NeurayLossTerm& a = terms[i];
+        nr::LossTerm& t = p.t[i];
+        if (a.kind != NEURAY_LOSS_RENDER && a.kind != NEURAY_LOSS_CONSIST && a.kind != NEURAY_LOSS_DEPTH) return fail("%s: term %d: unknown kind %d", what, i, a.kind);
+        if (!a.pred_dev || !a.ref_dev) return fail("%s: term %d: missing array", what, i);
+        if (a.rows < 1) return fail("%s: term %d: %d rows", what, i, a.rows);
+        if (a.n < 1 || a.n > (1 << 30)) return fail("%s: term %d: %d elements per row", what, i, a.n);
+        if (a.kind == NEURAY_LOSS_CONSIST && (a.inner < 1 || a.n % a.inner != 0)) return fail("%s: term %d: n=%d is not rn * dn with dn=%d", what, i, a.n, a.inner);
+        if (a.kind == NEURAY_LOSS_DEPTH) {
+            if (!a.coords_dev || !a.range_dev) return fail("%s: term %d: missing array", what, i);
+            if (a.h < 2 || a.w < 2) return fail("%s: term %d: the depth gather needs a map of at least 2 x 2 (h=%d w=%d)", what, i, a.h, a.w);
+            if ((long long)a.h * a.w > 0x7fffffffLL) return fail("%s: term %d: map %d x %d", what, i, a.h, a.w);
+            if (a.stride < 1) return fail("%s: term %d: element stride %d", what, i, a.stride);
+            if (a.smooth_l1 && !(a.beta >= 0.0f)) return fail("%s: term %d: beta %g", what, i, (double)a.beta);
+        }
+        if (backward && a.d_pred_dev && !a.grad_out_dev) return fail("%s: term %d: missing upstream gradient", what, i);
+        t.pred = a.pred_dev; t.ref = a.ref_dev; t.mask = a.kind == NEURAY_LOSS_CONSIST ? nullptr : a.mask_dev;
+        t.coords = a.coords_dev; t.range = a.range_dev; t.g_up = a.grad_out_dev; t.d_pred = a.d_pred_dev;
+        t.kind = a.kind; t.rows = a.rows; t.n = a.n; t.inner = a.kind == NEURAY_LOSS_CONSIST ? a.inner : 1;
+        t.stride = a.kind == NEURAY_LOSS_DEPTH ? a.stride : 1; t.h = a.h; t.w = a.w; t.coords_i64 = a.coords_i64 ? 1 : 0;
+        t.mask_u8 = a.kind == NEURAY_LOSS_RENDER && a.mask_u8 ? 1 : 0; t.smooth_l1 = a.smooth_l1 ? 1 : 0;
+        t.beta = a.beta; t.thresh = a.thresh;
+        t.chunks = (a.n + nr::kLossChunk - 1) / nr::kLossChunk;
+        if (blocks + (long long)t.chunks * a.rows > 0x7fffffffLL || rows > 0x7fffffff - a.rows) return fail("%s: too many rows", what);
+        t.block0 = (int)blocks; t.row0 = rows;
+        blocks += (long long)t.chunks * a.rows;
+        rows += a.rows;
+    }
+    p.nterms = n_terms; p.total_rows = rows;
+    return 0;
+}
+
+long long neuray_train_loss_workspace_bytes(const NeurayLossTerm* terms, int n_terms) {
+    nr::LossParams p = {};
+    long long blocks;
+    if (loss_params("neuray_train_loss_workspace_bytes", terms, n_terms, false, p, blocks)) return -1;
+    return blocks * 2 * (long long)sizeof(double);
+}
+
+int neuray_train_loss(const NeurayTrainLossArgs* a, void* stream) {
+    if (!a) return fail("neuray_train_loss: null args");
+    nr::LossParams p = {};
+    long long blocks;
+    if (int rc = loss_params("neuray_train_loss", a->terms, a->n_terms, false, p, blocks)) return rc;
+    if (!a->value_dev || !a->den_dev || !a->workspace_dev) return fail("neuray_train_loss: missing array");
+    p.ws = static_cast<double*>(a->workspace_dev); p.value = a->value_dev; p.den = a->den_dev;
+    NR_LAUNCH(nr::loss_partials_kernel, dim3((unsigned)blocks), dim3(nr::kLossThreads), 2 * nr::kLossThreads * sizeof(double), stream, p);
+    if (int rc = check_launch("neuray_train_loss")) return rc;
+    NR_LAUNCH(nr::loss_finish_kernel, dim3((unsigned)p.total_rows), dim3(64), 2 * 64 * sizeof(double), stream, p);
+    return check_launch("neuray_train_loss");
+}
+
+int neuray_train_loss_backward(const NeurayTrainLossArgs* a, void* stream) {
+    if (!a) return fail("neuray_train_loss_backward: null args");
+    nr::LossParams p = {};
+    long long blocks;
+    if (int rc = loss_params("neuray_train_loss_backward", a->terms, a->n_terms, true, p, blocks)) return rc;
+    if (!a->den_dev) return fail("neuray_train_loss_backward: missing array");
+    p.ws = nullptr; p.value = nullptr; p.den = a->den_dev;
+    NR_LAUNCH(nr::loss_backward_kernel, dim3((unsigned)blocks), dim3(nr::kLossThreads), 0, stream, p);
+    return check_launch("neuray_train_loss_backward");
 }
 
 #ifdef NR_B2_PROFILE

@@ -991,3 +991,101 @@ class RenderEngine:
         pixels = (y1 - y0) * (x1 - x0)
         psnr = torch.log10((255.0 * 255.0 * 3 * pixels) / sse.to(torch.float64)) * 10.0
         return {'sse': sse, 'ssim': val, 'psnr': psnr}
+
+    # ---- training losses (neuray_train_loss / neuray_train_loss_backward; network/loss.py) ---------------------------------
+    def _loss_table(self, terms, grads=None, d_preds=None):
+        if not 1 <= len(terms) <= _lib.LOSS_MAX_TERMS:
+            raise ValueError("neuray_amd.train_loss: %d terms (1 .. %d per loss call)" % (len(terms), _lib.LOSS_MAX_TERMS))
+        table = (_lib.NeurayLossTerm * len(terms))()
+        for i, t in enumerate(terms):
+            ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
+            table[i] = _lib.NeurayLossTerm(
+                t.pred.data_ptr(), t.ref.data_ptr(), ptr(t.mask), ptr(t.coords), ptr(t.range),
+                ptr(grads[i]) if grads is not None else None, ptr(d_preds[i]) if d_preds is not None else None,
+                t.kind, t.rows, t.n, t.inner, t.stride, t.h, t.w, int(t.coords is not None and t.coords.dtype == torch.int64),
+                int(t.mask is not None and t.mask.dtype != torch.float32), int(t.smooth_l1), float(t.beta), float(t.thresh))
+        return table
+
+    def train_loss(self, terms):
+        """One loss call (all terms of one loss object: LossTerm list, at most 4) in one forward launch pair.
+        -> (values float32 [sum of rows], in term order; den float64 [sum of rows], kept for train_loss_backward).
+        Buffers come from PyTorch's allocator, the launches go on the current stream, nothing is read back."""
+        table = self._loss_table(terms)
+        rows = sum(t.rows for t in terms)
+        ws_bytes = int(self.lib.neuray_train_loss_workspace_bytes(table, len(terms)))
+        if ws_bytes < 0:
+            self._check(1)
+        ws = self.empty(ws_bytes // 8, dtype=torch.float64)
+        values, den = self.empty(rows), self.empty(rows, dtype=torch.float64)
+        a = _lib.NeurayTrainLossArgs(C.cast(table, C.c_void_p), values.data_ptr(), den.data_ptr(), ws.data_ptr(), len(terms), 0)
+        self._check(self.lib.neuray_train_loss(C.byref(a), self._stream()))
+        return values, den
+
+    def train_loss_backward(self, terms, den, grads, needs):
+        """The backward of train_loss(terms) in one launch.  grads: per term the upstream gradient of its rows (float32 [rows] on the
+        device); needs: per term whether its prediction wants a gradient.  -> per term d_pred (contiguous, the prediction's shape) or None."""
+        grads = [self._f32(g).reshape(-1) if n else None for g, n in zip(grads, needs)]
+        d_preds = [self.empty(t.pred_shape) if n else None for t, n in zip(terms, needs)]
+        table = self._loss_table(terms, grads, d_preds)
+        a = _lib.NeurayTrainLossArgs(C.cast(table, C.c_void_p), None, den.data_ptr(), None, len(terms), 0)
+        self._check(self.lib.neuray_train_loss_backward(C.byref(a), self._stream()))
+        return d_preds
+
+
+class LossTerm:
+    """One term of a loss call for RenderEngine.train_loss: the tensors as the kernels read them (float32, on the engine's device;
+    nothing is converted silently - a wrong dtype is a TypeError).
+      render   pred / ref [b, n, 3], mask [b, n] (float32, bool or uint8) or None
+      consist  pred p1 / ref p0 [qn, rn, dn]
+      depth    pred [rfn, pn] (any element stride), ref [rfn, 1, h, w], coords [rfn, pn, 2] (float32 or int64), depth_range [rfn, 2],
+               mask: the noisy depth map [rfn, 1, h, w] of a gso scene or None"""
+
+    def __init__(self, device, kind, pred, ref, mask=None, coords=None, depth_range=None, smooth_l1=False, beta=0.0, thresh=0.0):
+        def f32(x, name):
+            if x.dtype != torch.float32:
+                raise TypeError("neuray_amd.train_loss: %s must be float32 (got %s)" % (name, x.dtype))
+            if x.device != device:
+                raise ValueError("neuray_amd.train_loss: %s is on %s, the engine on %s" % (name, x.device, device))
+            return x.detach()
+        pred, ref = f32(pred, 'the prediction'), f32(ref, 'the reference tensor').contiguous()
+        self.kind = {'render': _lib.LOSS_RENDER, 'consist': _lib.LOSS_CONSIST, 'depth': _lib.LOSS_DEPTH}[kind]
+        self.pred_shape = tuple(pred.shape)
+        self.inner, self.stride, self.h, self.w = 1, 1, 0, 0
+        self.coords = self.range = self.mask = None
+        self.smooth_l1, self.beta, self.thresh = bool(smooth_l1), beta, thresh
+        if kind == 'depth':
+            rfn, pn = pred.shape
+            if ref.shape[:2] != (rfn, 1) or ref.dim() != 4 or tuple(coords.shape) != (rfn, pn, 2) or tuple(depth_range.shape) != (rfn, 2):
+                raise ValueError("neuray_amd.train_loss: depth term shapes %s %s %s %s" % (tuple(pred.shape), tuple(ref.shape),
+                                                                                          tuple(coords.shape), tuple(depth_range.shape)))
+            if coords.dtype not in (torch.float32, torch.int64):
+                raise TypeError("neuray_amd.train_loss: depth_coords must be float32 or int64 (got %s)" % coords.dtype)
+            if pn > 1 and pred.stride(1) >= 1 and (rfn == 1 or pred.stride(0) == pn * pred.stride(1)):
+                self.stride = pred.stride(1)                      # e.g. mean[..., 0]: read in place
+            else:
+                pred = pred.contiguous()
+            self.rows, self.n, self.h, self.w = rfn, pn, ref.shape[2], ref.shape[3]
+            self.coords, self.range = coords.detach().contiguous(), f32(depth_range, 'depth_range').contiguous()
+            if mask is not None:
+                if mask.shape != ref.shape:
+                    raise ValueError("neuray_amd.train_loss: depth map shapes %s %s" % (tuple(ref.shape), tuple(mask.shape)))
+                self.mask = f32(mask, 'the noisy depth map').contiguous()
+        else:
+            pred = pred.contiguous()
+            if pred.shape != ref.shape or pred.dim() != 3 or (kind == 'render' and pred.shape[2] != 3):
+                raise ValueError("neuray_amd.train_loss: %s term shapes %s %s" % (kind, tuple(pred.shape), tuple(ref.shape)))
+            self.rows = pred.shape[0]
+            if kind == 'render':
+                self.n = pred.shape[1]
+                if mask is not None:
+                    if mask.dtype not in (torch.float32, torch.bool, torch.uint8):
+                        raise TypeError("neuray_amd.train_loss: ray_mask must be float32, bool or uint8 (got %s)" % mask.dtype)
+                    if mask.numel() != self.rows * self.n:
+                        raise ValueError("neuray_amd.train_loss: ray_mask %s for colours %s" % (tuple(mask.shape), tuple(pred.shape)))
+                    self.mask = mask.detach().contiguous()
+            else:
+                self.n, self.inner = pred.shape[1] * pred.shape[2], pred.shape[2]
+        self.pred, self.ref = pred, ref
+        for x in (self.mask, self.coords):
+            if x is not None and x.device != device:
+                raise ValueError("neuray_amd.train_loss: a tensor is on %s, the engine on %s" % (x.device, device))

@@ -28,6 +28,8 @@ Options swap the neighbouring per-image pieces too (each is the same arithmetic 
                     cached pixel lists (same np.random draws, same rays), no synchronous copy is left in a step
   metrics=True      network.metrics (PSNR_SSIM, VisualizeImage, compute_psnr, structural_similarity, name2metrics, ...) -> neuray_amd.metrics:
                     validation PSNR / SSIM on the HIP metrics kernels (the reference's module needs skimage)
+  loss=True         network.loss (RenderLoss, DepthLoss, ConsistencyLoss, name2loss) -> neuray_amd.loss: every term of a loss object in one
+                    fused forward and one fused backward launch (neuray_train_loss); off by default
 """
 import importlib
 import sys
@@ -62,7 +64,7 @@ def unpatch_renderer_class(cls):
             delattr(cls, name)
 
 
-def patch_reference(renderer_module=None, render_ops=False, init_nets=False, ft_host=False, render_loop=False, metrics=False):
+def patch_reference(renderer_module=None, render_ops=False, init_nets=False, ft_host=False, render_loop=False, metrics=False, loss=False):
     """Patch the reference's `network.renderer` (imported here if it is not yet; the reference tree must be importable).
     -> the patched module."""
     mod = renderer_module if renderer_module is not None else (
@@ -89,6 +91,8 @@ def patch_reference(renderer_module=None, render_ops=False, init_nets=False, ft_
         ref_init.get_diff_feats = hip_init.get_diff_feats
     if metrics:
         patch_metrics()
+    if loss:
+        patch_loss()
     return mod
 
 
@@ -131,6 +135,49 @@ def unpatch_metrics():
                 pkg.__dict__.pop('metrics', None)
             else:
                 pkg.metrics = attr
+
+
+_LOSS = {}
+
+
+def patch_loss():
+    """network.loss -> neuray_amd.loss, the way patch_metrics() installs the metrics: as sys.modules['network.loss'] (and the `network`
+    package's attribute) before the reference's module is imported; if it already is, the names it defines are replaced in place (the
+    trainer's `from network.loss import name2loss` done earlier keeps the dict object, so name2loss is updated in place too).  Idempotent."""
+    from . import loss as ours
+    if _LOSS:
+        return
+    ref = sys.modules.get('network.loss')
+    if ref is not None and ref is not ours:
+        _LOSS['names'] = (ref, {name: getattr(ref, name) for name in ours.REFERENCE_NAMES}, dict(ref.name2loss))
+        table = ref.name2loss
+        for name in ours.REFERENCE_NAMES:
+            setattr(ref, name, getattr(ours, name))
+        table.clear()                                    # the reference's own dict object: holders of it see ours
+        table.update(ours.name2loss)
+    else:
+        pkg = sys.modules.get('network')
+        _LOSS['module'] = (pkg, pkg.__dict__.get('loss') if pkg is not None else None)
+        sys.modules['network.loss'] = ours
+        if pkg is not None:
+            pkg.loss = ours
+
+
+def unpatch_loss():
+    if 'names' in _LOSS:
+        ref, saved, table = _LOSS.pop('names')
+        for name, value in saved.items():
+            setattr(ref, name, value)
+        saved['name2loss'].clear()
+        saved['name2loss'].update(table)
+    if 'module' in _LOSS:
+        pkg, attr = _LOSS.pop('module')
+        sys.modules.pop('network.loss', None)
+        if pkg is not None:
+            if attr is None:
+                pkg.__dict__.pop('loss', None)
+            else:
+                pkg.loss = attr
 
 
 RENDER_LOOP_METHODS = ('render', 'encode_views', '_early_query')
@@ -203,6 +250,7 @@ def unpatch_ft_host(ft_cls):
 
 def unpatch_reference(renderer_module=None):
     unpatch_metrics()
+    unpatch_loss()
     mod = renderer_module if renderer_module is not None else sys.modules.get('network.renderer')
     if mod is not None:
         unpatch_renderer_class(mod.NeuralRayBaseRenderer)

@@ -3,6 +3,7 @@
 neuray_direct_render_rays_backward, neuray_direct_render_points_backward, neuray_dist_decoder_rows_backward,
 neuray_interpolate_feats_backward).  Nothing here computes with PyTorch ops besides layout permutes and slicing."""
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import _lib
 
@@ -210,3 +211,54 @@ class DirectRenderFn(torch.autograd.Function):
                                                    packed=ctx.packed)
         grads = eng.unflatten_pass_grads(d_flat, run.state(), 'd.', 'a.')
         return (None, None, None, d_map if ctx.needs_input_grad[3] else None) + tuple(grads[k] for k, _ in run.dist_params())
+
+
+class LossCallFn(torch.autograd.Function):
+    """One loss call of network/loss.py (RenderLoss, ConsistencyLoss or DepthLoss: every term of one __call__) on neuray_train_loss:
+    (eng, specs, *tensors) -> one float32 [rows] value per term.  specs: per term (kind, options); tensors: per term the five slots
+    (prediction, reference, mask, coords, depth_range), None where a term has none.  One forward C-ABI call; autograd hands the
+    backward every term's upstream gradient at once, so it is one call too.  Only the predictions receive a gradient - the kernels
+    differentiate nothing else, so a reference, map or range that requires one is refused rather than dropped (the reference's
+    detached p0, hit_prob_nr, is the exception)."""
+    SLOTS = 5
+
+    @staticmethod
+    def forward(ctx, eng, specs, *tensors):
+        from ..engine import LossTerm
+        terms = []
+        for i, (kind, opts) in enumerate(specs):
+            pred, ref, mask, coords, rng = tensors[LossCallFn.SLOTS * i:LossCallFn.SLOTS * (i + 1)]
+            terms.append(LossTerm(eng.device, kind, pred, ref, mask=mask, coords=coords, depth_range=rng, **opts))
+        values, den = eng.train_loss(terms)
+        ctx.eng, ctx.terms, ctx.den = eng, terms, den
+        out, r = [], 0
+        for t in terms:
+            out.append(values[r:r + t.rows])
+            r += t.rows
+        return tuple(out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        needs = [ctx.needs_input_grad[2 + LossCallFn.SLOTS * i] for i in range(len(ctx.terms))]
+        grads = [g if g is not None or not n else torch.zeros(t.rows, device=ctx.eng.device) for g, n, t in zip(grads, needs, ctx.terms)]
+        d_preds = ctx.eng.train_loss_backward(ctx.terms, ctx.den, grads, needs)
+        ret = [None, None]
+        for d in d_preds:
+            ret += [d, None, None, None, None]
+        return tuple(ret)
+
+
+def loss_call(eng, terms):
+    """terms: list of (kind, options, prediction, reference, mask, coords, depth_range) -> list of per-term values (LossCallFn).
+    Under torch.no_grad(), or when no prediction requires a gradient, only the forward runs."""
+    specs, tensors = [], []
+    for kind, opts, pred, ref, mask, coords, rng in terms:
+        for name, x in (('reference tensor', None if kind == 'consist' else ref), ('mask / noisy depth map', mask), ('depth_coords', coords),
+                        ('depth_range', rng)):
+            if x is not None and x.requires_grad and torch.is_grad_enabled():
+                raise NotImplementedError("neuray_amd.loss: the %s of a %s term requires grad; the loss kernels differentiate the "
+                                          "predictions only" % (name, kind))
+        specs.append((kind, opts))
+        tensors += [pred, ref.detach() if kind == 'consist' else ref, mask, coords, rng]
+    return list(LossCallFn.apply(eng, specs, *tensors))
