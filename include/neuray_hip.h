@@ -359,6 +359,10 @@ long long neuray_conv3x3_x3_pack_bytes(int cin, int cout);
 int neuray_conv3x3_x3_pack(const float* w_dev, int cout, int cin, void* wpack_dev, void* wpack_t_dev, void* stream);
 int neuray_conv3x3_x3(const float* x_dev, const void* wpack_dev, const float* bias_dev, int n, int cin, int cout, int h, int w, int pad,
                       float* out_dev, void* stream);
+/* neuray_conv3x3_x3_relu: the same call with max(. + bias, 0) in the epilogue - F.relu(F.conv2d(x, w, b, padding=pad)) in one launch (the
+ *   twelve wide layers of the LPIPS network below).  Same arguments, same accumulation; neuray_conv3x3_x3 itself is unchanged. */
+int neuray_conv3x3_x3_relu(const float* x_dev, const void* wpack_dev, const float* bias_dev, int n, int cin, int cout, int h, int w, int pad,
+                           float* out_dev, void* stream);
 /* neuray_conv3x3_x3_wrw: the WEIGHT gradient of the same layers in the same arithmetic, straight from the NCHW tensors (the contraction runs
  *   over positions, which NCHW stores contiguously: no transposed copies): dy_dev [n][C_out][hp - 2][wp - 2] (the gradient of the layer's
  *   output), xp_dev [n][C_in][hp][wp] (the layer's pre-padded input) -> dw_dev [C_out][C_in][3][3] (overwritten).  wp must be even.
@@ -505,6 +509,27 @@ typedef struct NeurayImageMetricsArgs {
 } NeurayImageMetricsArgs;
 long long neuray_image_metrics_workspace_bytes(int n, int h, int w);
 int neuray_image_metrics(const NeurayImageMetricsArgs* args, void* stream);
+
+/* ---- LPIPS, the third number of eval.py (eval.py:16,24-27: lpips.LPIPS(net='vgg') on images scaled to [-1, 1]) - inference only.  The
+ * network is five blocks of 2, 2, 3, 3, 3 convolutions (3 x 3, padding 1, ReLU), a 2 x 2 max pool in front of blocks 2 to 5 and a tap behind
+ * every block; its widths and weights come from the caller.  These entry points are the pieces around neuray_conv3x3_x3_relu:
+ * neuray_lpips_stem: replaces the scaling layer and conv1_1 + ReLU.  img_dev: uint8 [n][h][w][3] with input_u8 (eval.py's arithmetic in
+ *   fp32: x = u8 / 255f, then x * 2 - 1) or fp32 [n][3][h][w] in [-1, 1]; shift3_host / scale3_host: the scaling layer's constants (host
+ *   arrays of 3 floats): x <- (x - shift[c]) / scale[c]; w_dev [C1][3][3][3], bias_dev [C1] (C1 <= 512) -> out_dev [n][C1][h][w] NCHW fp32.
+ *   The zero padding is in the scaled space.  Plain fp32 multiplies and adds over (input channel, ky, kx) in that order, then the bias.
+ * neuray_maxpool2x2: replaces F.max_pool2d(x, 2, 2): x_dev [planes][h][w] -> out_dev [planes][h / 2][w / 2] (floor: an odd last row or
+ *   column is dropped), planes = n * channels.
+ * neuray_lpips_head: one tap of the LPIPS sum for n pairs.  f0_dev [n][c][h][w], f1_dev the same (f1_stride 1) or ONE image compared with
+ *   every f0 (f1_stride 0), lin_dev [c] (any sign) -> out_dev[i * out_stride] (fp64) = the mean over the pixels of
+ *   sum_c lin[c] (f0[c] / s0 - f1[c] / s1)^2 with s = sqrt(sum_c f[c]^2) + 1e-10: fp64 throughout, two passes over the channels, fixed
+ *   reduction order - a pair's value does not depend on the rest of the batch.  workspace_dev: neuray_lpips_head_workspace_bytes(n, h, w)
+ *   bytes (-1: a shape no call accepts).  Two launches, no synchronisation. */
+int neuray_lpips_stem(const void* img_dev, int input_u8, const float* shift3_host, const float* scale3_host, const float* w_dev,
+                      const float* bias_dev, int n, int cout, int h, int w, float* out_dev, void* stream);
+int neuray_maxpool2x2(const float* x_dev, long long planes, int h, int w, float* out_dev, void* stream);
+long long neuray_lpips_head_workspace_bytes(int n, int h, int w);
+int neuray_lpips_head(const float* f0_dev, const float* f1_dev, const float* lin_dev, int n, int f1_stride, int c, int h, int w,
+                      void* workspace_dev, double* out_dev, int out_stride, void* stream);
 
 /* ---- training losses: network/loss.py (RenderLoss 57-77, ConsistencyLoss 29-44, DepthLoss 91-132; cfg loss [render, depth] /
  * [render, consist]) - one *loss call*: up to NEURAY_LOSS_MAX_TERMS terms of one loss object in one forward and one backward launch.

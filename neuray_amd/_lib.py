@@ -184,6 +184,7 @@ SYMBOLS = {
     'neuray_conv3x3_x3_pack_bytes': (C.c_longlong, [C.c_int, C.c_int]),
     'neuray_conv3x3_x3_pack': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'neuray_conv3x3_x3': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'neuray_conv3x3_x3_relu': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'neuray_conv3x3_x3_wrw_workspace_floats': (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'neuray_conv3x3_x3_wrw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'neuray_scale_shift_leaky': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_float, C.c_void_p]),
@@ -192,6 +193,12 @@ SYMBOLS = {
     'neuray_diff_feats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'neuray_image_metrics_workspace_bytes': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     'neuray_image_metrics': (C.c_int, [C.POINTER(NeurayImageMetricsArgs), C.c_void_p]),
+    'neuray_lpips_stem': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_void_p, C.c_void_p]),
+    'neuray_maxpool2x2': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'neuray_lpips_head_workspace_bytes': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    'neuray_lpips_head': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                    C.c_void_p]),
     'neuray_train_loss_workspace_bytes': (C.c_longlong, [C.POINTER(NeurayLossTerm), C.c_int]),
     'neuray_train_loss': (C.c_int, [C.POINTER(NeurayTrainLossArgs), C.c_void_p]),
     'neuray_train_loss_backward': (C.c_int, [C.POINTER(NeurayTrainLossArgs), C.c_void_p]),

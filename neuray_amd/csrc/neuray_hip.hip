@@ -8,6 +8,7 @@
 #include "nr_kernels_conv2d.h"
 #include "nr_kernels_metrics.h"
 #include "nr_kernels_loss.h"
+#include "nr_kernels_lpips.h"
 // the plain bf16-operand build is inference only; the fp32 build and the split build (hi + lo bf16 operands: fp32-grade products)
 // carry the training path
 #if defined(NR_BF16_QUADS) && !defined(NR_BF16_SPLIT)
@@ -144,13 +145,13 @@ int launch_points_cfg(const nr::PointParams& p, int vpw, int arith, void* stream
 }  // namespace
 
 namespace {
-template <int NT, int MTW, int WC = 1>
+template <int NT, int MTW, int WC = 1, bool RELU = false>
 void launch_conv2d_x3(const nr::Conv2dX3Params& p, int bands, void* stream) {
     const int lw = p.tw + 2, hp = p.h + 2 * p.pad;
     const long long q = (long long)p.n * hp * lw;
     const int per = nr::kC2Waves * NT * 16;
     const size_t smem = (size_t)nr::conv2d_x3_smem_bytes(NT, lw);
-    auto k = nr::conv2d_x3_kernel<NT, MTW, WC>;
+    auto k = nr::conv2d_x3_kernel<NT, MTW, WC, RELU>;
 #ifndef NEURAY_EMU
     if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 #endif
@@ -391,7 +392,9 @@ int neuray_conv3x3_x3_pack(const float* w, int cout, int cin, void* wpack, void*
     return check_launch("neuray_conv3x3_x3_pack");
 }
 
-int neuray_conv3x3_x3(const float* x, const void* wpack, const float* bias, int n, int cin, int cout, int h, int w, int pad, float* out, void* stream) {
+namespace {
+// relu: the entry point with the ReLU epilogue - the default tile shapes only (the NT / MTW overrides of the A/B tools do not apply)
+int conv3x3_x3_impl(bool relu, const float* x, const void* wpack, const float* bias, int n, int cin, int cout, int h, int w, int pad, float* out, void* stream) {
     if (!x || !wpack || !out) return fail("neuray_conv3x3_x3: null pointer");
     if (neuray_conv3x3_x3_pack_bytes(cin, cout) < 0)
         return fail("neuray_conv3x3_x3: (C_in, C_out) = (%d, %d): both must be multiples of 32", cin, cout);
@@ -423,6 +426,13 @@ int neuray_conv3x3_x3(const float* x, const void* wpack, const float* bias, int 
     if ((g_conv2d_mtw == 2 || g_conv2d_mtw == 4) && mt % g_conv2d_mtw == 0) mtw = g_conv2d_mtw;
     if ((size_t)nr::conv2d_x3_smem_bytes(nt, p.tw + 2) > 160 * 1024 || nr::conv2d_x3_positions(nt, p.tw + 2) > 64 * nr::conv2d_x3_max_passes(nt))
         return fail("neuray_conv3x3_x3: band of %d columns does not fit the LDS", p.tw);
+    if (relu) {
+        if ((size_t)nr::conv2d_x3_smem_bytes(4, p.tw + 2) > 160 * 1024 || nr::conv2d_x3_positions(4, p.tw + 2) > 64 * nr::conv2d_x3_max_passes(4))
+            return fail("neuray_conv3x3_x3: band of %d columns does not fit the LDS", p.tw);
+        if (mt >= 8 && (mt / 2) % 2 == 0 && nr::conv2d_x3_positions(4, p.tw + 2) % 128 == 0 && g_conv2d_wc != 1) launch_conv2d_x3<4, 2, 2, true>(p, bands, stream);
+        else launch_conv2d_x3<4, 2, 1, true>(p, bands, stream);
+        return check_launch("neuray_conv3x3_x3_relu");
+    }
     if (nt == 8 && mtw == 4) launch_conv2d_x3<8, 4>(p, bands, stream);
     else if (nt == 8) launch_conv2d_x3<8, 2>(p, bands, stream);
     else if (mtw == 4) launch_conv2d_x3<4, 4>(p, bands, stream);
@@ -431,6 +441,15 @@ int neuray_conv3x3_x3(const float* x, const void* wpack, const float* bias, int 
     else if (mt >= 8 && (mt / 2) % 2 == 0 && nr::conv2d_x3_positions(4, p.tw + 2) % 128 == 0 && g_conv2d_wc != 1) launch_conv2d_x3<4, 2, 2>(p, bands, stream);
     else launch_conv2d_x3<4, 2>(p, bands, stream);
     return check_launch("neuray_conv3x3_x3");
+}
+}  // namespace
+
+int neuray_conv3x3_x3(const float* x, const void* wpack, const float* bias, int n, int cin, int cout, int h, int w, int pad, float* out, void* stream) {
+    return conv3x3_x3_impl(false, x, wpack, bias, n, cin, cout, h, w, pad, out, stream);
+}
+
+int neuray_conv3x3_x3_relu(const float* x, const void* wpack, const float* bias, int n, int cin, int cout, int h, int w, int pad, float* out, void* stream) {
+    return conv3x3_x3_impl(true, x, wpack, bias, n, cin, cout, h, w, pad, out, stream);
 }
 
 namespace {
@@ -977,6 +996,58 @@ int neuray_image_metrics(const NeurayImageMetricsArgs* a, void* stream) {
     if (int rc = check_launch("neuray_image_metrics")) return rc;
     NR_LAUNCH(nr::image_metrics_reduce_kernel, dim3(p.n), dim3(64), 4 * 64 * 8, stream, p);
     return check_launch("neuray_image_metrics");
+}
+
+// ---- LPIPS (nr_kernels_lpips.h) -------------------------------------------------------------------------------------------------------
+int neuray_lpips_stem(const void* img, int input_u8, const float* shift3, const float* scale3, const float* w, const float* bias, int n, int cout, int h, int wd,
+                      float* out, void* stream) {
+    if (!img || !shift3 || !scale3 || !w || !bias || !out) return fail("neuray_lpips_stem: null pointer");
+    if (n < 1 || h < 1 || wd < 1 || cout < 1 || cout > nr::kLpStemMaxC) return fail("neuray_lpips_stem: bad shape n=%d cout=%d h=%d w=%d", n, cout, h, wd);
+    const long long pixels = (long long)n * h * wd;
+    if (pixels * cout * 4 >= 0x7fffff00LL) return fail("neuray_lpips_stem: the output must stay below 2^31 bytes");
+    nr::LpipsStemParams p;
+    p.img = img; p.wgt = w; p.bias = bias; p.out = out; p.n = n; p.cout = cout; p.h = h; p.w = wd; p.u8 = input_u8 ? 1 : 0;
+    for (int c = 0; c < 3; ++c) {
+        if (!(scale3[c] != 0.0f)) return fail("neuray_lpips_stem: scale[%d] = %g", c, (double)scale3[c]);
+        p.shift[c] = shift3[c]; p.scale[c] = scale3[c];
+    }
+    const size_t smem = (size_t)cout * 28 * sizeof(float);
+    auto k = input_u8 ? nr::lpips_stem_kernel<true> : nr::lpips_stem_kernel<false>;
+    NR_LAUNCH(k, dim3((unsigned)((pixels + nr::kLpThreads - 1) / nr::kLpThreads)), dim3(nr::kLpThreads), smem, stream, p);
+    return check_launch("neuray_lpips_stem");
+}
+
+int neuray_maxpool2x2(const float* x, long long planes, int h, int w, float* out, void* stream) {
+    if (!x || !out) return fail("neuray_maxpool2x2: null pointer");
+    if (planes < 1 || h < 2 || w < 2) return fail("neuray_maxpool2x2: bad shape planes=%lld h=%d w=%d", planes, h, w);
+    nr::MaxPoolParams p;
+    p.x = x; p.out = out; p.h = h; p.w = w; p.total = planes * (h / 2) * (w / 2);
+    const long long blocks = (p.total + nr::kLpThreads - 1) / nr::kLpThreads;
+    if (blocks > 0x7fffffffLL) return fail("neuray_maxpool2x2: %lld elements", p.total);
+    NR_LAUNCH(nr::maxpool2x2_kernel, dim3((unsigned)blocks), dim3(nr::kLpThreads), 0, stream, p);
+    return check_launch("neuray_maxpool2x2");
+}
+
+long long neuray_lpips_head_workspace_bytes(int n, int h, int w) {
+    if (n < 1 || h < 1 || w < 1) return -1;
+    const long long tiles = ((long long)h * w + nr::kLpTile - 1) / nr::kLpTile;
+    if (tiles * n > 0x7fffffffLL) return -1;
+    return tiles * n * (long long)sizeof(double);
+}
+
+int neuray_lpips_head(const float* f0, const float* f1, const float* lin, int n, int f1_stride, int c, int h, int w, void* workspace, double* out,
+                      int out_stride, void* stream) {
+    if (!f0 || !f1 || !lin || !workspace || !out) return fail("neuray_lpips_head: null pointer");
+    if (neuray_lpips_head_workspace_bytes(n, h, w) < 0 || c < 1 || f1_stride < 0 || f1_stride > 1 || out_stride < 1)
+        return fail("neuray_lpips_head: bad shape n=%d c=%d h=%d w=%d f1_stride=%d out_stride=%d", n, c, h, w, f1_stride, out_stride);
+    nr::LpipsHeadParams p;
+    p.f0 = f0; p.f1 = f1; p.lin = lin; p.ws = static_cast<double*>(workspace); p.out = out;
+    p.n = n; p.f1_stride = f1_stride; p.c = c; p.out_stride = out_stride; p.plane = (long long)h * w;
+    p.tiles = (int)((p.plane + nr::kLpTile - 1) / nr::kLpTile);
+    NR_LAUNCH(nr::lpips_head_tile_kernel, dim3((unsigned)(p.tiles * n)), dim3(nr::kLpThreads), 0, stream, p);
+    if (int rc = check_launch("neuray_lpips_head")) return rc;
+    NR_LAUNCH(nr::lpips_head_reduce_kernel, dim3((unsigned)n), dim3(64), 0, stream, p);
+    return check_launch("neuray_lpips_head");
 }
 
 // ---- training losses (nr_kernels_loss.h) --------------------------------------------------------------------------------------------

@@ -75,7 +75,8 @@ struct Conv2dX3Params {
     int tw;                  // output columns per band (blockIdx.z); lw = tw + 2
 };
 
-template <int NT, int MTW, int WC = 1>
+// RELU: max(. + bias, 0) in the epilogue (the VGG layers of LPIPS, nr_kernels_lpips.h); the accumulation is the same code
+template <int NT, int MTW, int WC = 1, bool RELU = false>
 __global__ void __launch_bounds__(64 * kC2Waves * WC) conv2d_x3_kernel(Conv2dX3Params p) {
     constexpr int MAXP = (conv2d_x3_max_passes(NT) + WC - 1) / WC;
     NR_DYNAMIC_SMEM(unsigned char, lds);
@@ -238,7 +239,11 @@ __global__ void __launch_bounds__(64 * kC2Waves * WC) conv2d_x3_kernel(Conv2dX3P
         NR_PRAGMA_UNROLL
         for (int mt = 0; mt < MTW; ++mt)
             NR_PRAGMA_UNROLL
-            for (int r = 0; r < 4; ++r) o[(size_t)(16 * mt + r) * oplane] = acc[t][mt][r] + bias[mt][r];
+            for (int r = 0; r < 4; ++r) {
+                const float val = acc[t][mt][r] + bias[mt][r];
+                if constexpr (RELU) o[(size_t)(16 * mt + r) * oplane] = val > 0.0f ? val : 0.0f;
+                else o[(size_t)(16 * mt + r) * oplane] = val;
+            }
     }
 }
 

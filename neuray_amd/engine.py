@@ -992,6 +992,61 @@ class RenderEngine:
         psnr = torch.log10((255.0 * 255.0 * 3 * pixels) / sse.to(torch.float64)) * 10.0
         return {'sse': sse, 'ssim': val, 'psnr': psnr}
 
+    # ---- LPIPS pieces (neuray_lpips_stem / neuray_conv3x3_x3_relu / neuray_maxpool2x2 / neuray_lpips_head; neuray_amd/lpips.py) --------
+    def _out(self, out, shape):
+        """`out`: a contiguous fp32 workspace tensor on the device with at least prod(shape) elements, or None -> a view / a new tensor"""
+        n = 1
+        for s in shape:
+            n *= int(s)
+        if out is None:
+            return self.empty(*shape)
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.device == self.device and out.numel() >= n
+        return out.view(-1)[:n].view(*shape)
+
+    def lpips_stem(self, img, shift, scale, weight, bias, out=None):
+        """img uint8 [n, h, w, 3] or fp32 [n, 3, h, w] in [-1, 1] (contiguous, on the device) -> relu(conv1_1((x - shift) / scale))
+        [n, C1, h, w] (neuray_lpips_stem); weight [C1, 3, 3, 3], bias [C1]"""
+        u8 = img.dtype == torch.uint8
+        n, h, w = (img.shape[0], img.shape[1], img.shape[2]) if u8 else (img.shape[0], img.shape[2], img.shape[3])
+        c1 = weight.shape[0]
+        assert img.is_contiguous() and img.device == self.device and (u8 or img.dtype == torch.float32) and img.shape[3 if u8 else 1] == 3
+        assert weight.is_contiguous() and weight.dtype == torch.float32 and tuple(weight.shape[1:]) == (3, 3, 3) and bias.numel() == c1
+        res = self._out(out, (n, c1, h, w))
+        self._check(self.lib.neuray_lpips_stem(img.data_ptr(), int(u8), (C.c_float * 3)(*shift), (C.c_float * 3)(*scale), weight.data_ptr(),
+                                               bias.data_ptr(), n, c1, h, w, res.data_ptr(), self._stream()))
+        return res
+
+    def conv3x3_x3_relu(self, x, pack, bias, cout, pad=1, out=None):
+        """relu(conv3x3_x3(x) + bias) in one launch (neuray_conv3x3_x3_relu); `out`: a workspace to write into"""
+        n, c, h, w = x.shape
+        assert x.is_contiguous() and x.dtype == torch.float32 and (bias is None or (bias.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == cout))
+        res = self._out(out, (n, cout, h + 2 * pad - 2, w + 2 * pad - 2))
+        self._check(self.lib.neuray_conv3x3_x3_relu(x.data_ptr(), pack.data_ptr(), bias.data_ptr() if bias is not None else None, n, c, cout, h, w,
+                                                    int(pad), res.data_ptr(), self._stream()))
+        return res
+
+    def maxpool2x2(self, x, out=None):
+        """x [n, c, h, w] contiguous fp32 -> F.max_pool2d(x, 2, 2) [n, c, h // 2, w // 2] (neuray_maxpool2x2)"""
+        n, c, h, w = x.shape
+        assert x.is_contiguous() and x.dtype == torch.float32
+        res = self._out(out, (n, c, h // 2, w // 2))
+        self._check(self.lib.neuray_maxpool2x2(x.data_ptr(), n * c, h, w, res.data_ptr(), self._stream()))
+        return res
+
+    def lpips_head(self, f0, f1, lin, out=None, column=0):
+        """One tap of LPIPS (neuray_lpips_head): f0 [n, c, h, w], f1 [n or 1, c, h, w], lin [c] -> float64 [n]: per pair the pixel mean of
+        sum_c lin[c] (f0[c] / |f0| - f1[c] / |f1|)^2.  With `out` (float64 [n, k], contiguous) the values go to out[:, column]."""
+        n, c, h, w = f0.shape
+        assert f0.is_contiguous() and f1.is_contiguous() and f0.dtype == f1.dtype == torch.float32 and tuple(f1.shape[1:]) == (c, h, w)
+        assert f1.shape[0] in (1, n) and lin.is_contiguous() and lin.dtype == torch.float32 and lin.numel() == c
+        if out is None:
+            out, column = self.empty(n, 1, dtype=torch.float64), 0
+        assert out.is_contiguous() and out.dtype == torch.float64 and out.shape[0] == n and 0 <= column < out.shape[1]
+        ws = self.empty(max(int(self.lib.neuray_lpips_head_workspace_bytes(n, h, w)), 8), dtype=torch.uint8)
+        self._check(self.lib.neuray_lpips_head(f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), n, 0 if (f1.shape[0] == 1 and n > 1) else 1, c, h, w,
+                                               ws.data_ptr(), out.data_ptr() + 8 * column, out.shape[1], self._stream()))
+        return out[:, column]
+
     # ---- training losses (neuray_train_loss / neuray_train_loss_backward; network/loss.py) ---------------------------------
     def _loss_table(self, terms, grads=None, d_preds=None):
         if not 1 <= len(terms) <= _lib.LOSS_MAX_TERMS:
