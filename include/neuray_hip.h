@@ -581,6 +581,10 @@ int neuray_mfma_selftest(const float* A_dev, const float* B_dev, float* D_dev, v
 /* ---- hardware self test of the lane-group sum behind the vector rows (v_permlane16_swap / v_permlane32_swap):
  * y[l] = (x[c] + x[c+16]) + (x[c+32] + x[c+48]) with c = l % 16, for the 64 lanes of one wave. */
 int neuray_group_sum_selftest(const float* x_dev, float* y_dev, void* stream);
+/* ---- the batched forms of that sum: x [4][64] -> y [7][64] for the 64 lanes of one wave.  y[j][l], j < 4: the lane-group sum of x[j] as
+ * above, obtained by summing the four registers together (lane group j receives total j) and gathering the totals back into every lane;
+ * y[4], y[5]: the two-value form on x[0], x[1]; y[6][l]: the lane-group sum of x[l / 16] (the scattered register itself). */
+int neuray_group_scatter_selftest(const float* x_dev, float* y_dev, void* stream);
 
 /* ---- hardware self test of NEURAY_ARITH_X3: D [16][16] = A [16][32] @ B [32][16] through the point kernel's operand path - both operands
  * split into three bf16 parts on the device, six v_mfma_f32_16x16x32_bf16 products, fp32 accumulation.  parts_dev (may be NULL):

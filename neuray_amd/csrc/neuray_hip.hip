@@ -947,6 +947,10 @@ int neuray_group_sum_selftest(const float* x, float* y, void* stream) {
     NR_LAUNCH(nr::group_sum_selftest_kernel, dim3(1), dim3(64), 0, stream, x, y);
     return check_launch("neuray_group_sum_selftest");
 }
+int neuray_group_scatter_selftest(const float* x, float* y, void* stream) {
+    NR_LAUNCH(nr::group_scatter_selftest_kernel, dim3(1), dim3(64), 0, stream, x, y);
+    return check_launch("neuray_group_scatter_selftest");
+}
 
 // ---- image metrics (nr_kernels_metrics.h) -------------------------------------------------------------------------------------------
 static void metrics_tiles(int y0, int y1, int x0, int x1, int& tiles_y, int& tiles_x) {

@@ -339,6 +339,22 @@ __device__ __forceinline__ void logistic_prob(float t, float lo, float hi, float
     hit = fmaf(c11 - c01, m1, (c10 - c00) * m0);
 }
 
+// The same for the two slots of a wave at once, on reduce-scattered parameters (layer_vec_scatter_2x2 / _1x2): mu, sd hold mixture
+// component j of slot s in lane group 2 j + s; t, aw, nu and the results hold slot s in lane groups s and 2 + s.  The four CDFs of a slot
+// pair are one instruction sequence instead of eight; each value goes through the operations of logistic_prob in the same order.
+__device__ __forceinline__ void logistic_prob_scattered(float t, float lo, float hi, float mu, float sd, float aw, float nu, bool use_vis,
+                                                        float& visibility, float& hit) {
+    const float near = t - lo, far = t + hi;
+    float cn = fmaf(0.5f, tanh_((near - mu) * sd), 0.5f), cf = fmaf(0.5f, tanh_((far - mu) * sd), 0.5f);
+    if (use_vis) { cn *= nu; cf *= nu; }
+    const float m0 = aw, m1 = 1.0f - aw;
+    float v0, v1, h0, h1;
+    nr_group_halves(1.0f - cn, v0, v1);           // component 0 sits in lane groups 0, 1, component 1 in 2, 3
+    nr_group_halves(cf - cn, h0, h1);
+    visibility = fmaf(v1, m1, v0 * m0);
+    hit = fmaf(h1, m1, h0 * m0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // MFMA MLP layers (layout: nr_layout.h).  NT = point tiles (16 points each) processed per wave.
 //   xq[t][4*kq + j] : B operands of the quad K-steps,  x1[t][k1] : B operands of the single K-steps
@@ -537,9 +553,9 @@ __device__ __forceinline__ void layer_prefetch(WS W, int lane, VecPre<L>& p) {
     for (int i = 0; i < VecPre<L>::N * VecPre<L>::TI; ++i) p.w[i] = wld4(W, (lane >> 4) * 16, (vec_offset(L, AR) + i * 16) * 4);
     p.b = wld4(W, (lane >> 4) * 16, vec_bias_offset(L, AR) * 4);
 }
-// out[t][j] = b_j + sum_f w_j[f] x[t][f], identical in the four lane groups; x in the D layout (4 registers per tile)
+// a[t][j] = this lane group's part of sum_f w_j[f] x[t][f] (its 4 * tiles features); x in the D layout (4 registers per tile)
 template <int L, int NT, int KX>
-__device__ __forceinline__ void layer_vec(const VecPre<L>& p, const float (&x)[NT][KX], float (&out)[NT][kVec[L].n]) {
+__device__ __forceinline__ void layer_vec_partial(const VecPre<L>& p, const float (&x)[NT][KX], float (&a)[NT][kVec[L].n]) {
     constexpr int N = kVec[L].n, TI = kVec[L].tiles;
     static_assert(KX >= 4 * TI, "operand array too small");
     NR_PRAGMA_UNROLL
@@ -554,10 +570,41 @@ __device__ __forceinline__ void layer_vec(const VecPre<L>& p, const float (&x)[N
                 a2 = nr_v2_fma(nr_v2_make(p.w[j * TI + ti].x, p.w[j * TI + ti].y), nr_v2_make(x[t][4 * ti], x[t][4 * ti + 1]), a2);
                 a2 = nr_v2_fma(nr_v2_make(p.w[j * TI + ti].z, p.w[j * TI + ti].w), nr_v2_make(x[t][4 * ti + 2], x[t][4 * ti + 3]), a2);
             }
-            const float a = a2.x + a2.y;
-            const float bj = j == 0 ? p.b.x : (j == 1 ? p.b.y : (j == 2 ? p.b.z : p.b.w));
-            out[t][j] = nr_group_sum(a) + bj;
+            a[t][j] = a2.x + a2.y;
         }
+}
+// out[t][j] = b_j + sum_f w_j[f] x[t][f], identical in the four lane groups
+template <int L, int NT, int KX>
+__device__ __forceinline__ void layer_vec(const VecPre<L>& p, const float (&x)[NT][KX], float (&out)[NT][kVec[L].n]) {
+    constexpr int N = kVec[L].n;
+    float a[NT][N];
+    layer_vec_partial<L, NT>(p, x, a);
+    NR_PRAGMA_UNROLL
+    for (int t = 0; t < NT; ++t)
+        NR_PRAGMA_UNROLL
+        for (int j = 0; j < N; ++j) {
+            const float bj = j == 0 ? p.b.x : (j == 1 ? p.b.y : (j == 2 ? p.b.z : p.b.w));
+            out[t][j] = nr_group_sum(a[t][j]) + bj;
+        }
+}
+// The same rows for the TWO slots of a wave, reduce-scattered (nr_group_scatter4 / 2, nr_platform.h): one register holds the rows of both
+// slots, each in its own lane group(s), so that the activation behind the row is evaluated once instead of once per value and lane
+// group.  Every value is the sum + bias layer_vec gives, bit for bit.
+//   two rows (L_DFIN_M, L_DFIN_V): lane group 2 j + s holds row j of slot s  (g = the lane's group)
+template <int L, int KX>
+__device__ __forceinline__ float layer_vec_scatter_2x2(const VecPre<L>& p, const float (&x)[2][KX], int g) {
+    static_assert(kVec[L].n >= 2, "two rows");
+    float a[2][kVec[L].n];
+    layer_vec_partial<L, 2>(p, x, a);
+    return nr_group_scatter4(a[0][0], a[1][0], a[0][1], a[1][1]) + (g >= 2 ? p.b.y : p.b.x);
+}
+//   one row J: lane groups s and 2 + s hold slot s
+template <int L, int J, int KX>
+__device__ __forceinline__ float layer_vec_scatter_1x2(const VecPre<L>& p, const float (&x)[2][KX]) {
+    static_assert(kVec[L].n > J, "row outside the layer");
+    float a[2][kVec[L].n];
+    layer_vec_partial<L, 2>(p, x, a);
+    return nr_group_scatter2(a[0][J], a[1][J]) + (J == 0 ? p.b.x : (J == 1 ? p.b.y : (J == 2 ? p.b.z : p.b.w)));
 }
 template <int L, int NT, class WS, int KX>
 __device__ __forceinline__ void layer_vec(WS W, int lane, const float (&x)[NT][KX], float (&out)[NT][kVec[L].n]) {

@@ -255,7 +255,11 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
     // rows 4 j + r; with one wave the 16 rows run on into the result region).  A wave's region is read by others only between the two
     // barriers of an all-reduce, the rows are written after one and consumed before the next phase barrier: no extra synchronisation.
     auto xrow = [&](int mo, int r) -> float* {
-        if constexpr (AR == AR_X3) return red + ((size_t)(mo % nw) * RMAX + (mo / nw) * 4 + r) * 64;
+        // (OWN == 1: four or more waves, tile mo belongs to wave mo - the row is a compile-time constant for the callers' constant mo, r.
+        // Left to the general form, hipcc evaluates the twelve quotient / remainder offsets of mo = 1..3 in the prologue and parks them
+        // in VGPR lanes for the whole tile loop: a v_readlane per use)
+        if constexpr (AR == AR_X3 && OWN == 1) return red + ((size_t)mo * RMAX + r) * 64;
+        else if constexpr (AR == AR_X3) return red + ((size_t)(mo % nw) * RMAX + (mo / nw) * 4 + r) * 64;
         else return xch + (mo * 4 + r) * 64;
     };
     auto make_w = [&]() {
@@ -263,8 +267,6 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
         else return nr_make_wbuf(p.weights, sizeof(float) * kPackedPassFloats);
     };
     const auto W = make_w();
-    const float* __restrict__ qc = p.que_const;
-    const float qnearp = qc[24], qfarp = qc[25], qinv = qc[27];
     const float w_m1 = (float)(p.w - 1), h_m1 = (float)(p.h - 1);
     const float inv_w_m1 = 1.0f / w_m1, inv_h_m1 = 1.0f / h_m1, inv_rfn = 1.0f / (float)p.rfn;
     const size_t fmap = (size_t)p.fh * p.fw * 32, imap = (size_t)p.h * p.w * 4;
@@ -276,7 +278,6 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
     const int dn = p.dn;
     const bool use_vis = p.use_vis != 0;
     const bool folded = AR == AR_X3 || (!SAVE && p.folded != 0);
-    const bool dbg_lane = DBG && (g == 0);
     // XCD-aware tile map: workgroup b runs on XCD b % 8 (observed dispatch order; used for speed only).  Giving every
     // XCD a contiguous run of tiles keeps the texels that neighbouring samples / rays share inside one private L2
     // instead of fetching them into all eight (the grid is a multiple of 8).
@@ -318,15 +319,22 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
         const int wave_t = wave;
 #endif
         const int gg = glane >> 4;
+        const bool dbg_lane = DBG && (gg == 0);
+        // the arguments the geometry block and the record stores read, fetched per tile (NR_ARGS_HERE): the query constants alone are
+        // 27 scalars that otherwise stay in SGPRs across the whole tile body
+        const auto* pt = NR_ARGS_HERE(PointParams, p);
         // ---------------- geometry (a2-a6) ----------------------------------------------------
         int pidx; bool pvalid;
         float mask[NS], dlt[NS][4], tref[NS], pu[NS], pv[NS], lo, hi;
         int soff_f[NS], soff_c[NS];                    // byte offsets of the slot's view inside the feature / colour maps
         {
             int pi, ray, smp;
+            const float* __restrict__ qc = pt->que_const;
+            const float qnearp = qc[24], qfarp = qc[25], qinv = qc[27];
+            const int dn = pt->dn, npts = pt->rn * dn;         // (shadow the launch-wide copies: the same values, read here)
             if constexpr (TR) {
 #if NR_POINT_TILE_ORDER == 1      // sample-major: consecutive tiles are neighbouring ray blocks at one sample index
-                const int tix = base >> 4, nrb = (p.rn + 15) / 16;
+                const int tix = base >> 4, nrb = (pt->rn + 15) / 16;
                 smp = tix / nrb;
                 const int rb = tix - smp * nrb;
 #else                             // ray-block-major: consecutive tiles walk along the rays of one block
@@ -334,8 +342,8 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                 smp = tix - rb * dn;
 #endif
                 ray = rb * 16 + c;
-                pvalid = ray < p.rn;
-                ray = pvalid ? ray : p.rn - 1;
+                pvalid = ray < pt->rn;
+                ray = pvalid ? ray : pt->rn - 1;
                 pi = ray * dn + smp;
             } else {
                 pi = base + c;
@@ -345,14 +353,19 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                 smp = pi - ray * dn;
             }
             pidx = pi;
-            const Ray r = make_ray<false>(qc, p.coords[2 * ray], p.coords[2 * ray + 1]);
-            const float* drow = p.depth + (size_t)ray * dn;
+            const Ray r = make_ray<false>(qc, pt->coords[2 * ray], pt->coords[2 * ray + 1]);
+            const float* drow = pt->depth + (size_t)ray * dn;
             const float d = drow[smp];
             // half intervals in normalised inverse depth (render_ops.py:46-52, dist_decoder.py:34-38); feature path:
             // hardware reciprocals (they feed only the logistic CDFs)
-            const float s_c = norm_inv_depth_fast(d, qnearp, qfarp, qinv);
-            const float s_n = norm_inv_depth_fast(drow[smp + 1 < dn ? smp + 1 : smp], qnearp, qfarp, qinv);
-            const float s_p = norm_inv_depth_fast(drow[smp > 0 ? smp - 1 : 0], qnearp, qfarp, qinv);
+            // the sample's and its two neighbours' normalised inverse depths: lane group 0 / 1 / 2 evaluates its own one, an all-gather hands
+            // the three to every lane (one reciprocal chain instead of three on every lane; the same operations on the same inputs)
+            float s_c, s_n, s_p, s_x;
+            {
+                const int nxt = smp + 1 < dn ? smp + 1 : smp, prv = smp > 0 ? smp - 1 : 0;
+                const float dg = drow[gg == 0 ? smp : (gg == 1 ? nxt : prv)];
+                nr_group_gather4(norm_inv_depth_fast(dg, qnearp, qfarp, qinv), s_c, s_n, s_p, s_x);
+            }
             const float half_c = (smp == dn - 1) ? 500000.0f : (s_n - s_c) * 0.5f;
             const float half_p = (s_c - s_p) * 0.5f;
             hi = half_c;
@@ -363,10 +376,10 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
             NR_PRAGMA_UNROLL
             for (int s = 0; s < NS; ++s) {
                 const int vraw = wave_t * VPW + s;
-                const bool vok = vraw < p.rfn;                // padding view when rfn % VPW != 0: masked out
-                const int view = vok ? vraw : p.rfn - 1;
-                const float* __restrict__ vc = p.view_const + view * kViewConst;
-                Proj pr = project_point<false>(vc, px, py, pz, (float)p.w, (float)p.h);   // u, v, z, mask stay exact
+                const bool vok = vraw < pt->rfn;                // padding view when rfn % VPW != 0: masked out
+                const int view = vok ? vraw : pt->rfn - 1;
+                const float* __restrict__ vc = pt->view_const + view * kViewConst;
+                Proj pr = project_point<false>(vc, px, py, pz, (float)pt->w, (float)pt->h);   // u, v, z, mask stay exact
                 if (!vok) pr.mask = 0.0f;
                 mask[s] = pr.mask;
                 dlt[s][0] = pr.dirx - r.qx; dlt[s][1] = pr.diry - r.qy; dlt[s][2] = pr.dirz - r.qz;
@@ -374,7 +387,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                 tref[s] = norm_inv_depth_fast(fmaxf(pr.z, 1e-5f), vc[15], vc[16], vc[17]);
                 pu[s] = pr.u; pv[s] = pr.v;
                 if (dbg_lane && pvalid && vok) {
-                    float* d_ = p.dbg + ((size_t)pi * p.rfn + view) * kDbgFields;
+                    float* d_ = pt->dbg + ((size_t)pi * pt->rfn + view) * kDbgFields;
                     d_[0] = pr.mask; d_[1] = pr.u; d_[2] = pr.v; d_[3] = pr.z;
                 }
                 soff_f[s] = view * (int)(fmap * sizeof(float)); soff_c[s] = view * (int)(imap * sizeof(float));
@@ -384,6 +397,11 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
         // ---------------- the tile body for NA active slots (slots [0, NA) are the active ones) --------------------------
         auto tile = [&](auto na_tag) NR_LAMBDA_INLINE {
             constexpr int NA = decltype(na_tag)::value, NA1 = NA > 0 ? NA : 1, IDLE = NS - NA;
+            // SC: the narrow rows of the two slots are summed over the lane groups as ONE batch (reduce-scatter), their activations evaluated
+            // once per batch and handed back by an all-gather (nr_platform.h nr_group_scatter4) - instead of a sum, and an activation in
+            // all four lane groups, per value.  The one-slot body and the training forward keep the single-value form; the values agree bit
+            // for bit, so a point's result does not depend on the body it runs through.
+            constexpr bool SC = NA == 2 && !SAVE;
             // gathers (a7): the 20 tap loads of a slot are all issued before anything is blended, so they share one memory
             // round trip (left alone hipcc serialises load -> wait -> blend per map: 3 dependent round trips per slot).
             // Measured: +5% whole-job; holding two slots' taps (160 registers) or staggering slot s+1's loads into slot s's
@@ -451,6 +469,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
             {
                 float h1[NA1][8], h2[NA1][8], fm[NA1][2], fv[NA1][2], fa[NA1][1];
                 float mu0[NA1], mu1[NA1], s0[NA1], s1[NA1], aw[NA1], nu[NA1];
+                float mu_g = 0.0f, sd_g = 0.0f, aw_g = 0.0f, nu_g = 1.0f;      // SC: the same, reduce-scattered (logistic_prob_scattered)
                 LayerPreT<L_DV2, AR> p_dv2; VecPre<L_DFIN_V> p_fv;
                 const auto W1 = phase_enter<PH_DIST_M, HAS_VIS>(wl, W, seq0, true, wave_t, nw, lane);
                 if constexpr (NA > 0) {
@@ -467,7 +486,8 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
 #endif
                     layer_fwd<L_DM2, NA, ACT_ELU>(W1, lane, p_dm2, operand<AR>(h1), none, h2, p_fm);
                     layer_prefetch<L_DV1>(W1, lane, p_dv1);
-                    layer_vec<L_DFIN_M, NA>(p_fm, h2, fm);
+                    if constexpr (SC) mu_g = softplus(layer_vec_scatter_2x2<L_DFIN_M>(p_fm, h2, gg));
+                    else layer_vec<L_DFIN_M, NA>(p_fm, h2, fm);
 #ifdef NR_PROBE_PRE
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s)
@@ -483,11 +503,14 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     layer_prefetch<L_DV2>(W2, lane, p_dv2);
                     layer_fwd<L_DV2, NA, ACT_ELU>(W2, lane, p_dv2, operand<AR>(h1), none, h2, p_fv);
                     layer_prefetch<L_DA1>(W2, lane, p_da1);
-                    layer_vec<L_DFIN_V, NA>(p_fv, h2, fv);
-                    NR_PRAGMA_UNROLL
-                    for (int s = 0; s < NA; ++s) {
-                        mu0[s] = softplus(fm[s][0]); mu1[s] = softplus(fm[s][1]);
-                        s0[s] = softplus(fv[s][0]) + p.var_bias; s1[s] = softplus(fv[s][1]) + p.var_bias;
+                    if constexpr (SC) sd_g = softplus(layer_vec_scatter_2x2<L_DFIN_V>(p_fv, h2, gg)) + pt->var_bias;
+                    else {
+                        layer_vec<L_DFIN_V, NA>(p_fv, h2, fv);
+                        NR_PRAGMA_UNROLL
+                        for (int s = 0; s < NA; ++s) {
+                            mu0[s] = softplus(fm[s][0]); mu1[s] = softplus(fm[s][1]);
+                            s0[s] = softplus(fv[s][0]) + pt->var_bias; s1[s] = softplus(fv[s][1]) + pt->var_bias;
+                        }
                     }
 #ifdef NR_PROBE_PRE
                     layer_prefetch<L_DA2>(W2, lane, p_da2);
@@ -499,7 +522,8 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     layer_fwd<L_DA1, NA, ACT_ELU>(W2, lane, p_da1, o_fray, none, h1, p_da2);
 #endif
                     layer_fwd<L_DA2, NA, ACT_ELU>(W2, lane, p_da2, operand<AR>(h1), none, h2, p_fa);
-                    layer_vec<L_DFIN_A, NA>(p_fa, h2, fa);
+                    if constexpr (SC) aw_g = sigmoidf(layer_vec_scatter_1x2<L_DFIN_A, 0>(p_fa, h2));
+                    else layer_vec<L_DFIN_A, NA>(p_fa, h2, fa);
                 }
                 if constexpr (HAS_VIS) {
                     const auto W2s = phase_enter<PH_DIST_S, HAS_VIS>(wl, W, seq0, true, wave_t, nw, lane);
@@ -509,19 +533,39 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         layer_prefetch<L_DS1>(W2s, lane, p_ds1);
                         layer_fwd<L_DS1, NA, ACT_ELU>(W2s, lane, p_ds1, o_fray, none, h1, p_ds2);
                         layer_fwd<L_DS2, NA, ACT_ELU>(W2s, lane, p_ds2, operand<AR>(h1), none, h2, p_fs);
-                        layer_vec<L_DFIN_S, NA>(p_fs, h2, fs);
-                        NR_PRAGMA_UNROLL
-                        for (int s = 0; s < NA; ++s) { aw[s] = sigmoidf(fa[s][0]); nu[s] = sigmoidf(fs[s][0]); }
+                        if constexpr (SC) nu_g = sigmoidf(layer_vec_scatter_1x2<L_DFIN_S, 0>(p_fs, h2));
+                        else {
+                            layer_vec<L_DFIN_S, NA>(p_fs, h2, fs);
+                            NR_PRAGMA_UNROLL
+                            for (int s = 0; s < NA; ++s) { aw[s] = sigmoidf(fa[s][0]); nu[s] = sigmoidf(fs[s][0]); }
+                        }
                     }
-                } else {
+                } else if constexpr (!SC) {
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s) { aw[s] = sigmoidf(fa[s][0]); nu[s] = 1.0f; }
                 }
+                float vh_[2][NA1];                              // visibility, hit of the slots before the mask
+                if constexpr (SC) {
+                    // lane group 2 j + s evaluates the CDFs of mixture component j of slot s
+                    float v_, h_;
+                    logistic_prob_scattered((gg & 1) ? tref[1] : tref[0], lo, hi, mu_g, sd_g, aw_g, nu_g, use_vis && HAS_VIS, v_, h_);
+                    nr_group_gather2(v_, vh_[0][0], vh_[0][1]);
+                    nr_group_gather2(h_, vh_[1][0], vh_[1][1]);
+                    if constexpr (DBG) {
+                        const int vraw = wave_t * VPW + (gg & 1);
+                        if (pvalid && vraw < p.rfn) {
+                            float* d_ = pt->dbg + ((size_t)pidx * pt->rfn + vraw) * kDbgFields;
+                            d_[6 + (gg >> 1)] = mu_g; d_[8 + (gg >> 1)] = sd_g;
+                            if (gg < 2) { d_[10] = aw_g; d_[11] = nu_g; }
+                        }
+                    }
+                } else {
+                    NR_PRAGMA_UNROLL
+                    for (int s = 0; s < NA; ++s) logistic_prob(tref[s], lo, hi, mu0[s], mu1[s], s0[s], s1[s], aw[s], nu[s], use_vis && HAS_VIS, vh_[0][s], vh_[1][s]);
+                }
                 NR_PRAGMA_UNROLL
                 for (int s = 0; s < NA; ++s) {
-                    float v_, h_;
-                    logistic_prob(tref[s], lo, hi, mu0[s], mu1[s], s0[s], s1[s], aw[s], nu[s], use_vis && HAS_VIS, v_, h_);
-                    vis[s] = v_ * mask[s]; hit[s] = h_ * mask[s];
+                    vis[s] = vh_[0][s] * mask[s]; hit[s] = vh_[1][s] * mask[s];
                     const int vraw = wave_t * VPW + s;
                     if constexpr (SAVE) {
                         if (g == 0 && vraw < p.rfn && vraw < 8) {
@@ -530,9 +574,9 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         }
                     }
                     if (dbg_lane && pvalid && vraw < p.rfn) {
-                        float* d_ = p.dbg + ((size_t)pidx * p.rfn + vraw) * kDbgFields;
-                        d_[4] = hit[s]; d_[5] = vis[s]; d_[6] = mu0[s]; d_[7] = mu1[s]; d_[8] = s0[s]; d_[9] = s1[s];
-                        d_[10] = aw[s]; d_[11] = nu[s];
+                        float* d_ = pt->dbg + ((size_t)pidx * pt->rfn + vraw) * kDbgFields;
+                        d_[4] = hit[s]; d_[5] = vis[s];
+                        if constexpr (!SC) { d_[6] = mu0[s]; d_[7] = mu1[s]; d_[8] = s0[s]; d_[9] = s1[s]; d_[10] = aw[s]; d_[11] = nu[s]; }
                     }
                 }
             }
@@ -549,7 +593,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     float x1[NA][1];
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s)
-                        x1[s][0] = sel4(g, (hit[s] - 0.5f) * 2.0f, (vis[s] - 0.5f) * 2.0f, 0.0f, 0.0f);
+                        x1[s][0] = sel4(gg, (hit[s] - 0.5f) * 2.0f, (vis[s] - 0.5f) * 2.0f, 0.0f, 0.0f);
                     if constexpr (AR == AR_X3) {                     // (always the folded pack)
                         layer_fwd<L_PE1, NA, ACT_RELU>(W3, lane, p_pe1, o_fray, x1, e, p_rd1);
                     } else if (folded) {
@@ -574,17 +618,30 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                 {
                     float x1[NA][1], h[NA][4], df[NA][8], dc[NA][3];
                     NR_PRAGMA_UNROLL
-                    for (int s = 0; s < NA; ++s) x1[s][0] = sel4(g, dlt[s][0], dlt[s][1], dlt[s][2], dlt[s][3]);
+                    for (int s = 0; s < NA; ++s) x1[s][0] = sel4(gg, dlt[s][0], dlt[s][1], dlt[s][2], dlt[s][3]);
                     layer_fwd<L_RD1, NA, ACT_ELU>(W3, lane, p_rd1, o_none, x1, h, p_rd2);
                     layer_prefetch<L_RD2>(W3, lane, p_rd2v);
                     layer_fwd<L_RD2, NA, ACT_ELU>(W3, lane, p_rd2, operand<AR>(h), none, df, last);
-                    layer_vec<L_RD2, NA>(p_rd2v, h, dc);          // the three rgb rows of ray_dir_fc.2
+                    if constexpr (SC) {                           // the three rgb rows of ray_dir_fc.2: rows 0, 1 of both slots, then row 2
+                        float a[2][3];
+                        layer_vec_partial<L_RD2, 2>(p_rd2v, h, a);
+                        const float e01 = elu(nr_group_scatter4(a[0][0], a[1][0], a[0][1], a[1][1]) + (gg >= 2 ? p_rd2v.b.y : p_rd2v.b.x));
+                        const float e2 = elu(nr_group_scatter2(a[0][2], a[1][2]) + p_rd2v.b.z);
+                        nr_group_gather4(e01, dc[0][0], dc[1][0], dc[0][1], dc[1][1]);
+                        nr_group_gather2(e2, dc[0][2], dc[1][2]);
+                    } else {
+                        layer_vec<L_RD2, NA>(p_rd2v, h, dc);
+                        NR_PRAGMA_UNROLL
+                        for (int s = 0; s < NA; ++s)
+                            NR_PRAGMA_UNROLL
+                            for (int j = 0; j < 3; ++j) dc[s][j] = elu(dc[s][j]);
+                    }
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s) {
                         NR_PRAGMA_UNROLL
                         for (int k = 0; k < 8; ++k) gi[s][k] = fimg[s][k] + df[s][k];
                         NR_PRAGMA_UNROLL
-                        for (int j = 0; j < 3; ++j) gr[s][j] = rgb[s][j] + elu(dc[s][j]);
+                        for (int j = 0; j < 3; ++j) gr[s][j] = rgb[s][j] + dc[s][j];
                     }
                 }
             }
@@ -596,9 +653,12 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                 layer_prefetch<L_NF1>(W4, lane, p_nf1);
                 if constexpr (AR == AR_X3) { e3 = split_operand(e); layer_fwd<L_NF1, NA, ACT_ELU>(W4, lane, p_nf1, e3, none, h, p_nf2); }
                 else layer_fwd<L_NF1, NA, ACT_ELU>(W4, lane, p_nf1, e, none, h, p_nf2);
-                layer_vec<L_NF2, NA>(p_nf2, h, o);
-                NR_PRAGMA_UNROLL
-                for (int s = 0; s < NA; ++s) sn[s] = sigmoidf(o[s][0]);
+                if constexpr (SC) nr_group_gather2(sigmoidf(layer_vec_scatter_1x2<L_NF2, 0>(p_nf2, h)), sn[0], sn[1]);
+                else {
+                    layer_vec<L_NF2, NA>(p_nf2, h, o);
+                    NR_PRAGMA_UNROLL
+                    for (int s = 0; s < NA; ++s) sn[s] = sigmoidf(o[s][0]);
+                }
             }
             // ---------------- cross-view weighted mean / variance       ibrnet.py:334-340 ---------------------
             // Each statistic is all-reduced over the views and immediately consumed by the owner waves as a K-slice of
@@ -663,19 +723,19 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         for (int j = 0; j < 3; ++j) { const float d_ = gr[s][j] - st[8 + j]; part[s][8 + j] = wk[s] * (d_ * d_); }
                     }
                     if constexpr (BG_RES) {
-                        if (k == 0) bg_accumulate<NT, OWN, 0>(bgres, g, wave_t, nw, st, accg);
-                        else bg_accumulate<NT, OWN, 2>(bgres, g, wave_t, nw, st, accg);
+                        if (k == 0) bg_accumulate<NT, OWN, 0>(bgres, gg, wave_t, nw, st, accg);
+                        else bg_accumulate<NT, OWN, 2>(bgres, gg, wave_t, nw, st, accg);
                     } else {
-                        if (k == 0) bg_accumulate<NT, OWN, 0>(W, glane, g, wave_t, nw, st, accg);
-                        else bg_accumulate<NT, OWN, 2>(W, glane, g, wave_t, nw, st, accg);
+                        if (k == 0) bg_accumulate<NT, OWN, 0>(W, glane, gg, wave_t, nw, st, accg);
+                        else bg_accumulate<NT, OWN, 2>(W, glane, gg, wave_t, nw, st, accg);
                     }
                     view_allreduce<NA, IDLE, 11, RMAX, RED_SUM>(part, sv, red, wave_t, nw, lane);
                     if constexpr (BG_RES) {
-                        if (k == 0) bg_accumulate<NT, OWN, 1>(bgres, g, wave_t, nw, sv, accg);
-                        else bg_accumulate<NT, OWN, 3>(bgres, g, wave_t, nw, sv, accg);
+                        if (k == 0) bg_accumulate<NT, OWN, 1>(bgres, gg, wave_t, nw, sv, accg);
+                        else bg_accumulate<NT, OWN, 3>(bgres, gg, wave_t, nw, sv, accg);
                     } else {
-                        if (k == 0) bg_accumulate<NT, OWN, 1>(W, glane, g, wave_t, nw, sv, accg);
-                        else bg_accumulate<NT, OWN, 3>(W, glane, g, wave_t, nw, sv, accg);
+                        if (k == 0) bg_accumulate<NT, OWN, 1>(W, glane, gg, wave_t, nw, sv, accg);
+                        else bg_accumulate<NT, OWN, 3>(W, glane, gg, wave_t, nw, sv, accg);
                     }
                     if constexpr (SAVE) {                          // every wave_t holds the statistics: wave_t 2k % nw writes the mean, (2k + 1) % nw the variance
                         float* d_ = p.saved + (size_t)(base / 16) * kSavedTileFloats + (kSavedStatRow + 22 * k) * 64 + lane;
@@ -726,7 +786,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     for (int s = 0; s < NA; ++s) {
                         NR_PRAGMA_UNROLL
                         for (int k = 0; k < 8; ++k) { xq[s][k] = gi[s][k]; xq[s][8 + k] = e[s][k]; }
-                        x1[s][0] = sel4(g, gr[s][0], gr[s][1], gr[s][2], 0.0f);
+                        x1[s][0] = sel4(gg, gr[s][0], gr[s][1], gr[s][2], 0.0f);
                     }
                     layer_prefetch<L_BV0>(W4, lane, p_bv0);
                     NR_PRAGMA_UNROLL
@@ -800,11 +860,17 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     layer_prefetch<L_VF2>(W5, lane, p_vf2);
                     layer_prefetch<L_VF2>(W5, lane, p_vf2v);
                     layer_fwd<L_VF2, NA, ACT_ELU>(W5, lane, p_vf2, operand<AR>(h), none, y, p_v21);
-                    layer_vec<L_VF2, NA>(p_vf2v, h, yv);          // row 32: the visibility logit
+                    // row 32: the visibility logit; sigmoid on an ELU output: quirk A.9.4
+                    if constexpr (SC) nr_group_gather2(sigmoidf(elu(layer_vec_scatter_1x2<L_VF2, 0>(p_vf2v, h))), yv[0][0], yv[1][0]);
+                    else {
+                        layer_vec<L_VF2, NA>(p_vf2v, h, yv);
+                        NR_PRAGMA_UNROLL
+                        for (int s = 0; s < NA; ++s) yv[s][0] = sigmoidf(elu(yv[s][0]));
+                    }
                     float visp[NA];
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s) {
-                        visp[s] = sigmoidf(elu(yv[s][0])) * mask[s];      // sigmoid on an ELU output: quirk A.9.4
+                        visp[s] = yv[s][0] * mask[s];
                         NR_PRAGMA_UNROLL
                         for (int k = 0; k < 8; ++k) { x[s][k] = x[s][k] + y[s][k]; xin[s][k] = x[s][k] * visp[s]; }
                     }
@@ -814,25 +880,31 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         layer_fwd_scaled<L_V21, NA, ACT_ELU>(W5, lane, p_v21, x3, visp, h, p_v22);       // W (x vis') = vis' (W x)
                     } else layer_fwd<L_V21, NA, ACT_ELU>(W5, lane, p_v21, xin, none, h, p_v22);
                     layer_prefetch<L_RF1>(W5, lane, p_rf1);
-                    layer_vec<L_V22, NA>(p_v22, h, o);
+                    if constexpr (SC) nr_group_gather2(sigmoidf(layer_vec_scatter_1x2<L_V22, 0>(p_v22, h)), o[0][0], o[1][0]);
+                    else {
+                        layer_vec<L_V22, NA>(p_v22, h, o);
+                        NR_PRAGMA_UNROLL
+                        for (int s = 0; s < NA; ++s) o[s][0] = sigmoidf(o[s][0]);
+                    }
                     NR_PRAGMA_UNROLL
-                    for (int s = 0; s < NA; ++s) vis2[s] = sigmoidf(o[s][0]) * mask[s];
+                    for (int s = 0; s < NA; ++s) vis2[s] = o[s][0] * mask[s];
                     float x1[NA][2], h16[NA][4], h8[NA][4];
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s) {
-                        x1[s][0] = sel4(g, vis2[s], dlt[s][0], dlt[s][1], dlt[s][2]);
-                        x1[s][1] = sel4(g, dlt[s][3], 0.0f, 0.0f, 0.0f);
+                        x1[s][0] = sel4(gg, vis2[s], dlt[s][0], dlt[s][1], dlt[s][2]);
+                        x1[s][1] = sel4(gg, dlt[s][3], 0.0f, 0.0f, 0.0f);
                     }
                     if constexpr (AR == AR_X3) layer_fwd<L_RF1, NA, ACT_ELU>(W5, lane, p_rf1, x3, x1, h16, p_rf2);
                     else layer_fwd<L_RF1, NA, ACT_ELU>(W5, lane, p_rf1, x, x1, h16, p_rf2);
                     layer_fwd<L_RF2, NA, ACT_ELU>(W5, lane, p_rf2, operand<AR>(h16), none, h8, p_rf3);
-                    layer_vec<L_RF3, NA>(p_rf3, h8, o);
+                    if constexpr (SC) nr_group_gather2(layer_vec_scatter_1x2<L_RF3, 0>(p_rf3, h8), o[0][0], o[1][0]);
+                    else layer_vec<L_RF3, NA>(p_rf3, h8, o);
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s) {
                         z[s] = mask[s] > 0.0f ? o[s][0] : -1e9f;
                         const int vraw = wave_t * VPW + s;
                         if (dbg_lane && pvalid && vraw < p.rfn) {
-                            float* d_ = p.dbg + ((size_t)pidx * p.rfn + vraw) * kDbgFields;
+                            float* d_ = pt->dbg + ((size_t)pidx * pt->rfn + vraw) * kDbgFields;
                             d_[12] = sn[s]; d_[13] = visp[s]; d_[14] = vis2[s]; d_[15] = z[s];
                         }
                     }
@@ -917,7 +989,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     for (int k = 0; k < 8; ++k) { const float d_ = x[s][k] - big[k]; v8[s][k] = wh[s] * (d_ * d_); }
                 NR_PRAGMA_UNROLL
                 for (int k = 0; k < 8; ++k) xq[0][k] = big[k];
-                x1[0][0] = sel4(g, meanw * inv_rfn, 0.0f, 0.0f, 0.0f);
+                x1[0][0] = sel4(gg, meanw * inv_rfn, 0.0f, 0.0f, 0.0f);
                 NR_PRAGMA_UNROLL
                 for (int j = 0; j < OWN; ++j) {
                     const int mo = wave_t + j * nw;
@@ -966,15 +1038,15 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                 for (int k = 0; k < 16; ++k) h[0][k] = xrow(k >> 2, k & 3)[lane];
                 layer_fwd<L_GF2, NT, ACT_ELU>(W, glane, h, nonet, G);
                 if (pvalid)
-                    *reinterpret_cast<float4*>(p.point_out + (size_t)pidx * kPointRec + 4 * g) = make_float4(G[0][0], G[0][1], G[0][2], G[0][3]);
+                    *reinterpret_cast<float4*>(pt->point_out + (size_t)pidx * kPointRec + 4 * g) = make_float4(G[0][0], G[0][1], G[0][2], G[0][3]);
                 if constexpr (SAVE) {
                     NR_PRAGMA_UNROLL
                     for (int r = 0; r < 4; ++r) p.saved[(size_t)(base / 16) * kSavedTileFloats + (kSavedGRow + r) * 64 + lane] = G[0][r];
                 }
             }
-            if (wave_t == (nw > 1 ? 1 : 0) && g == 0) {
+            if (wave_t == (nw > 1 ? 1 : 0) && gg == 0) {
                 if (pvalid)
-                    *reinterpret_cast<float4*>(p.point_out + (size_t)pidx * kPointRec + 16) = make_float4(big[9], big[10], big[11], msum);
+                    *reinterpret_cast<float4*>(pt->point_out + (size_t)pidx * kPointRec + 16) = make_float4(big[9], big[10], big[11], msum);
             }
         };
 
@@ -1816,6 +1888,18 @@ __global__ void x3_selftest_kernel(const float* __restrict__ A /*16x32*/, const 
 
 __global__ void group_sum_selftest_kernel(const float* __restrict__ x, float* __restrict__ y) {
     y[threadIdx.x & 63] = nr_group_sum(x[threadIdx.x & 63]);
+}
+
+// the batched forms (nr_platform.h): x [4][64] -> y [7][64].  Rows 0..3: the four-value reduce-scatter of x[0..3] handed back by the
+// all-gather - in every lane the four nr_group_sum results; rows 4, 5: the same for the two-value form on x[0], x[1]; row 6: the
+// reduce-scattered register itself (lane group j holds the total of x[j])
+__global__ void group_scatter_selftest_kernel(const float* __restrict__ x, float* __restrict__ y) {
+    const int l = threadIdx.x & 63;
+    const float s4 = nr_group_scatter4(x[l], x[64 + l], x[128 + l], x[192 + l]);
+    float a, b, c, d, e, f;
+    nr_group_gather4(s4, a, b, c, d);
+    nr_group_gather2(nr_group_scatter2(x[l], x[64 + l]), e, f);
+    y[l] = a; y[64 + l] = b; y[128 + l] = c; y[192 + l] = d; y[256 + l] = e; y[320 + l] = f; y[384 + l] = s4;
 }
 
 }  // namespace nr

@@ -249,6 +249,21 @@ __device__ __forceinline__ int nr_opaque_zero() { int z; asm volatile("v_mov_b32
 __device__ __forceinline__ int nr_opaque_szero() { int z; asm volatile("s_mov_b32 %0, 0" : "=s"(z)); return z; }
 #endif
 
+// The kernel's argument block through a pointer the compiler cannot see through, re-made where it is called (once per tile of the point
+// kernel): what is read through it - a pointer, a size, a constant derived from them - is a scalar load next to its use instead of a
+// loop-invariant SGPR that lives across the whole tile loop; with ~100 SGPRs busy in the tile body hipcc parks those in VGPR lanes and
+// reads them back with v_readlane (+ s_nop) inside the loop.  T = the struct that is the kernel's only parameter, p = that parameter.
+#ifdef NEURAY_EMU
+#define NR_ARGS_HERE(T, p) (&(p))
+#else
+template <class T> __device__ __forceinline__ const __attribute__((address_space(4))) T* nr_args_here() {
+    unsigned long long q = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(q));
+    return (const __attribute__((address_space(4))) T*)q;      // (constant address space: scalar loads)
+}
+#define NR_ARGS_HERE(T, p) (nr_args_here<T>())
+#endif
+
 // forces a value to be computed HERE (an empty volatile asm that "modifies" it): LLVM's IR-level sinking otherwise moves
 // pure arithmetic down to the block of its first use, across sched_barriers, and keeps the operands alive instead
 #ifdef NEURAY_EMU
@@ -315,6 +330,80 @@ __device__ __forceinline__ float nr_group_sum(float t) {
     const unsigned v = __builtin_bit_cast(unsigned, s);
     const v2f b = __builtin_bit_cast(v2f, (v2u)__builtin_amdgcn_permlane32_swap(v, v, false, false));  // [lo lo], [hi hi]
     return b.x + b.y;
+}
+#endif
+
+// Reduce-scatter / all-gather over the four lane groups: the batched form of nr_group_sum.  Summing four partial-sum registers one by
+// one takes 8 swaps (+ 8 copies, the swaps being destructive) and leaves every total replicated, so whatever is evaluated on it runs
+// four times on identical inputs.  Here the swaps exchange DIFFERENT values: three swaps sum four registers and leave total j in lane
+// group j alone; the consumer evaluates its activation once, on all four values, and nr_group_gather4 hands the results back in the
+// replicated layout.  Every total is associated (g0 + g1) + (g2 + g3) as in nr_group_sum (fp32 addition commutes): bit-identical.
+//   nr_group_scatter4(a, b, c, d): lane group 0 / 1 / 2 / 3 receives the total of a / b / c / d
+//   nr_group_scatter2(a, b):       lane groups 0, 2 receive the total of a, lane groups 1, 3 that of b
+//   nr_group_gather4(x, ...):      a / b / c / d = the value x holds in lane group 0 / 1 / 2 / 3, in every lane
+//   nr_group_gather2(x, a, b):     a / b = the value x holds in lane groups 0, 2 / 1, 3 (x as left by nr_group_scatter2)
+//   nr_group_halves(x, lo, hi):    lo / hi = the value x holds in lane group (g & 1) / 2 + (g & 1)
+#ifdef NEURAY_EMU
+static inline float nr_group_scatter4(float a, float b, float c, float d) {
+    const int l = emu::my_lane(), col = l & 15, g = l >> 4;
+    float w[4];
+    for (int k = 0; k < 4; ++k) {
+        const float fa = emu_shfl_f(a, col + 16 * k), fb = emu_shfl_f(b, col + 16 * k), fc = emu_shfl_f(c, col + 16 * k), fd = emu_shfl_f(d, col + 16 * k);
+        w[k] = g == 0 ? fa : (g == 1 ? fb : (g == 2 ? fc : fd));
+    }
+    return (w[0] + w[1]) + (w[2] + w[3]);
+}
+static inline float nr_group_scatter2(float a, float b) { return nr_group_scatter4(a, b, a, b); }
+static inline void nr_group_gather4(float x, float& a, float& b, float& c, float& d) {
+    const int col = emu::my_lane() & 15;
+    a = emu_shfl_f(x, col); b = emu_shfl_f(x, col + 16); c = emu_shfl_f(x, col + 32); d = emu_shfl_f(x, col + 48);
+}
+static inline void nr_group_gather2(float x, float& a, float& b) {
+    const int l = emu::my_lane();
+    a = emu_shfl_f(x, l & 47); b = emu_shfl_f(x, (l & 47) + 16);
+}
+static inline void nr_group_halves(float x, float& lo, float& hi) {
+    const int l = emu::my_lane();
+    lo = emu_shfl_f(x, l & 31); hi = emu_shfl_f(x, (l & 31) + 32);
+}
+#else
+__device__ __forceinline__ float nr_group_scatter4(float a, float b, float c, float d) {
+    // (whole-vector bit casts: see nr_group_sum)
+    typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const v2f p = __builtin_bit_cast(v2f, (v2u)__builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false));   // [a0 b0 a2 b2], [a1 b1 a3 b3]
+    const v2f q = __builtin_bit_cast(v2f, (v2u)__builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, c), __builtin_bit_cast(unsigned, d), false, false));   // [c0 d0 c2 d2], [c1 d1 c3 d3]
+    const float s = p.x + p.y, t = q.x + q.y;                                                          // [a01 b01 a23 b23], [c01 d01 c23 d23]
+    const v2f r = __builtin_bit_cast(v2f, (v2u)__builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, s), __builtin_bit_cast(unsigned, t), false, false));   // [a01 b01 c01 d01], [a23 b23 c23 d23]
+    return r.x + r.y;
+}
+__device__ __forceinline__ float nr_group_scatter2(float a, float b) {
+    typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const v2f p = __builtin_bit_cast(v2f, (v2u)__builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false));   // [a0 b0 a2 b2], [a1 b1 a3 b3]
+    const unsigned s = __builtin_bit_cast(unsigned, p.x + p.y);                                       // [a01 b01 a23 b23]
+    const v2f r = __builtin_bit_cast(v2f, (v2u)__builtin_amdgcn_permlane32_swap(s, s, false, false)); // [a01 b01 a01 b01], [a23 b23 a23 b23]
+    return r.x + r.y;
+}
+__device__ __forceinline__ void nr_group_halves(float x, float& lo, float& hi) {
+    typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    const v2f r = __builtin_bit_cast(v2f, (v2u)__builtin_amdgcn_permlane32_swap(u, u, false, false)); // [x0 x1 x0 x1], [x2 x3 x2 x3]
+    lo = r.x; hi = r.y;
+}
+__device__ __forceinline__ void nr_group_gather2(float x, float& a, float& b) {
+    typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const unsigned u = __builtin_bit_cast(unsigned, x);
+    const v2f r = __builtin_bit_cast(v2f, (v2u)__builtin_amdgcn_permlane16_swap(u, u, false, false)); // [x0 x0 x2 x2], [x1 x1 x3 x3]
+    a = r.x; b = r.y;
+}
+__device__ __forceinline__ void nr_group_gather4(float x, float& a, float& b, float& c, float& d) {
+    float lo, hi;
+    nr_group_halves(x, lo, hi);
+    nr_group_gather2(lo, a, b);
+    nr_group_gather2(hi, c, d);
 }
 #endif
 
