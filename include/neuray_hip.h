@@ -594,6 +594,35 @@ int neuray_x3_selftest(const float* A_dev, const float* B_dev, float* D_dev, flo
  * NEURAY_ARITH_*: hipOccupancyMaxActiveBlocksPerMultiprocessor with the kernel's registers and LDS.  -1 = not built / not a device build. */
 int neuray_points_resident_workgroups(int arith, int rfn);
 
+/* ---- visibility-guided coarse pass (cfg['hip_coarse_pass'] = 'visibility'): the coarse hit probabilities that place the fine samples,
+ * from the input views' visibility alone - predict_alpha_values_dr + decode_alpha_value + alpha_values2hit_prob (renderer.py:85-94,
+ * 121-123; the hit_prob_dr of direct rendering) without the aggregation network and without a per-(point, view) record.  fp32 MFMA; not in
+ * the bf16-operand builds.
+ * neuray_visibility_points, per sample point: projection, the ray_feats gather, the dist-decoder heads and compute_prob per view (the
+ * point kernel's arithmetic), then alpha_dev [rn*dn] = sum_v vis_v alpha_v / (sum_v vis_v + 1e-5) over the views in ascending index
+ * (`ground` where no view sees the point) and nvalid_dev [rn*dn] = the number of views that see it.  packed_weights_dev: the pass's
+ * neuray_pack_pass_weights[_folded] buffer.  rfn 1 .. NEURAY_MAX_VIEWS, dn 3 .. NEURAY_MAX_SAMPLES.
+ * neuray_visibility_rays, per ray: hit_prob_dev [rn][dn] = alpha_values2hit_prob(sigmoid(alpha)) and ray_mask_dev [rn] (may be NULL) =
+ * more than point_num samples are seen by more than view_num views (renderer.py:195-198). */
+typedef struct NeurayVisibilityArgs {
+    const float* query_const_dev;
+    const float* view_const_dev;       /* [rfn][NEURAY_VIEW_CONST] */
+    const float* coords_dev;           /* [rn][2] pixel (x,y) */
+    const float* depth_dev;            /* [rn][dn] ascending sample depths */
+    const float* ray_feats_nhwc_dev;   /* [rfn][fh][fw][32] */
+    const float* packed_weights_dev;
+    int rfn, rn, dn, h, w, fh, fw;
+    int has_vis_head;    /* this pass's decoder has a vis_decoder */
+    int use_vis;         /* the COARSE decoder's cfg['use_vis'] */
+    float var_bias;      /* dist_decoder cfg['bias_val'] (0.05) */
+    float ground;        /* cfg['alpha_value_ground_state'] */
+    float* alpha_dev;
+    int* nvalid_dev;
+} NeurayVisibilityArgs;
+int neuray_visibility_points(const NeurayVisibilityArgs* args, void* stream);
+int neuray_visibility_rays(const float* alpha_dev, const int* nvalid_dev, int rn, int dn, int view_num, int point_num, float* hit_prob_dev,
+                           unsigned char* ray_mask_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,13 @@ class NeurayTrainLossArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('terms', 'value_dev', 'den_dev', 'workspace_dev')] + [('n_terms', C.c_int), ('reserved', C.c_int)]
 
 
+class NeurayVisibilityArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('query_const_dev', 'view_const_dev', 'coords_dev', 'depth_dev', 'ray_feats_nhwc_dev',
+                                          'packed_weights_dev')] + \
+        [(n, C.c_int) for n in ('rfn', 'rn', 'dn', 'h', 'w', 'fh', 'fw', 'has_vis_head', 'use_vis')] + \
+        [('var_bias', C.c_float), ('ground', C.c_float), ('alpha_dev', C.c_void_p), ('nvalid_dev', C.c_void_p)]
+
+
 LOSS_RENDER, LOSS_CONSIST, LOSS_DEPTH = 0, 1, 2   # NeurayLossTerm.kind (include/neuray_hip.h NEURAY_LOSS_*)
 LOSS_MAX_TERMS = 4
 
@@ -203,6 +210,8 @@ SYMBOLS = {
     'neuray_train_loss_workspace_bytes': (C.c_longlong, [C.POINTER(NeurayLossTerm), C.c_int]),
     'neuray_train_loss': (C.c_int, [C.POINTER(NeurayTrainLossArgs), C.c_void_p]),
     'neuray_train_loss_backward': (C.c_int, [C.POINTER(NeurayTrainLossArgs), C.c_void_p]),
+    'neuray_visibility_points': (C.c_int, [C.POINTER(NeurayVisibilityArgs), C.c_void_p]),
+    'neuray_visibility_rays': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

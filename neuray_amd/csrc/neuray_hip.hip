@@ -17,6 +17,9 @@
 #include "nr_kernels_bwd2.h"
 #endif
 #include "nr_kernels_dr.h"          // (after the NR_INFERENCE_ONLY decision: its backward half is training only)
+#ifndef NR_BF16_QUADS
+#include "nr_kernels_vis.h"         // (fp32 MFMA only: the bf16-operand builds leave the visibility entries returning an error)
+#endif
 #include "nr_pack.h"
 #include "../../include/neuray_hip.h"
 
@@ -1122,6 +1125,53 @@ int neuray_train_loss_backward(const NeurayTrainLossArgs* a, void* stream) {
     p.ws = nullptr; p.value = nullptr; p.den = a->den_dev;
     NR_LAUNCH(nr::loss_backward_kernel, dim3((unsigned)blocks), dim3(nr::kLossThreads), 0, stream, p);
     return check_launch("neuray_train_loss_backward");
+}
+
+int neuray_visibility_points(const NeurayVisibilityArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_visibility_points: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_visibility_points: null args");
+    if (a->rfn < 1 || a->rfn > NEURAY_MAX_VIEWS) return fail("neuray_visibility_points: rfn=%d outside [1,%d]", a->rfn, NEURAY_MAX_VIEWS);
+    if (a->dn <= 2 || a->dn > NEURAY_MAX_SAMPLES || a->rn < 1) return fail("neuray_visibility_points: bad rn=%d dn=%d (dn in [3,%d])", a->rn, a->dn, NEURAY_MAX_SAMPLES);
+    if (a->h < 2 || a->w < 2 || a->fh < 1 || a->fw < 1) return fail("neuray_visibility_points: bad shape h=%d w=%d fh=%d fw=%d", a->h, a->w, a->fh, a->fw);
+    if (a->use_vis && !a->has_vis_head) return fail("neuray_visibility_points: use_vis set but the decoder has no vis head");
+    if ((long long)a->rn * a->dn > 0x7fffffffLL / 2) return fail("neuray_visibility_points: rn*dn too large for one call");
+    if ((long long)a->rfn * a->fh * a->fw * 128 >= 0x7fffff00LL) return fail("neuray_visibility_points: the ray_feats maps must stay below 2^31 bytes");
+    if (!a->query_const_dev || !a->view_const_dev || !a->coords_dev || !a->depth_dev || !a->ray_feats_nhwc_dev || !a->packed_weights_dev)
+        return fail("neuray_visibility_points: missing input array");
+    if (!a->alpha_dev || !a->nvalid_dev) return fail("neuray_visibility_points: alpha_dev / nvalid_dev missing");
+    nr::VisParams p;
+    p.que_const = a->query_const_dev; p.view_const = a->view_const_dev; p.coords = a->coords_dev; p.depth = a->depth_dev;
+    p.ray_feats = a->ray_feats_nhwc_dev; p.weights = a->packed_weights_dev; p.alpha = a->alpha_dev; p.nvalid = a->nvalid_dev;
+    p.rfn = a->rfn; p.rn = a->rn; p.dn = a->dn; p.h = a->h; p.w = a->w; p.fh = a->fh; p.fw = a->fw;
+    p.use_vis = a->use_vis; p.var_bias = a->var_bias; p.ground = a->ground;
+    const int nwaves = (a->rfn + 1) / 2;
+    const long long tiles = (long long)((a->rn + 15) / 16) * a->dn;
+    int grid = grid_for(tiles, 1, NR_POINT_GRID);         // the point kernel's persistent-style grid
+    if (tiles >= 4096 && grid > tiles / NR_POINT_MIN_TILES) grid = (int)(tiles / NR_POINT_MIN_TILES);
+    grid = (grid + 7) / 8 * 8;                             // (the XCD-aware tile map needs a multiple of 8)
+    const size_t smem = nr::vis_smem_bytes();
+    // the vis head is evaluated only when compute_prob consumes it (as neuray_render_points)
+    if (a->has_vis_head && a->use_vis) NR_LAUNCH(nr::vis_points_kernel<true>, dim3(grid), dim3(64 * nwaves), smem, stream, p);
+    else NR_LAUNCH(nr::vis_points_kernel<false>, dim3(grid), dim3(64 * nwaves), smem, stream, p);
+    return check_launch("neuray_visibility_points");
+#endif
+}
+
+int neuray_visibility_rays(const float* alpha, const int* nvalid, int rn, int dn, int view_num, int point_num, float* hit_prob,
+                           unsigned char* ray_mask, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)alpha; (void)nvalid; (void)rn; (void)dn; (void)view_num; (void)point_num; (void)hit_prob; (void)ray_mask; (void)stream;
+    return fail("neuray_visibility_rays: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (rn < 1 || dn < 1 || dn > NEURAY_MAX_SAMPLES) return fail("neuray_visibility_rays: bad shape rn=%d dn=%d", rn, dn);
+    if (!alpha || !nvalid || !hit_prob) return fail("neuray_visibility_rays: alpha / nvalid / hit_prob missing");
+    const int grid = grid_for(rn, 64, 256 * 8);
+    NR_LAUNCH(nr::vis_rays_kernel, dim3(grid), dim3(64), 0, stream, alpha, nvalid, rn, dn, view_num, point_num, hit_prob, ray_mask);
+    return check_launch("neuray_visibility_rays");
+#endif
 }
 
 #ifdef NR_B2_PROFILE

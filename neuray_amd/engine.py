@@ -871,6 +871,32 @@ class RenderEngine:
                                                        pix.data_ptr(), s))
         return {'hit_prob': hit, 'pixel': pix, 'alpha': alpha, 'colors': colors}
 
+    def visibility_pass(self, qconst, views, coords, depth, packed, use_vis, var_bias=0.05, ground=-15.0, ray_mask_view_num=2,
+                        ray_mask_point_num=8):
+        """The visibility-guided coarse pass (cfg['hip_coarse_pass'] = 'visibility'; renderer.py:85-94,121-123 without the aggregation
+        network): -> dict(hit_prob [rn,dn], alpha [rn,dn] (logits), ray_mask [rn] bool, nvalid [rn,dn] int32).  hit_prob / alpha are
+        direct_render's, bit for bit; ray_mask is render_pass's.  Inference only, fp32 library only."""
+        if self.variant != 'fp32':
+            raise NotImplementedError("neuray_amd: visibility_pass lives in the fp32 library (variant=%r)" % (self.variant,))
+        coords, depth = self._f32(coords), self._f32(depth)
+        rn, dn = depth.shape
+        assert coords.shape == (rn, 2)
+        alpha, nvalid = self.empty(rn, dn), self.empty(rn, dn, dtype=torch.int32)
+        s = self._stream()
+        a = _lib.NeurayVisibilityArgs(
+            qconst.data_ptr(), views.view_const.data_ptr(), coords.data_ptr(), depth.data_ptr(), views.ray_feats.data_ptr(),
+            packed.dev.data_ptr(), views.rfn, rn, dn, views.h, views.w, views.fh, views.fw, int(packed.has_vis_head), int(bool(use_vis)),
+            float(var_bias), float(ground), alpha.data_ptr(), nvalid.data_ptr())
+        ev = self._event_pair()
+        self._check(self.lib.neuray_visibility_points(C.byref(a), s))
+        self._event_done(ev, 'vis_points', rn * dn)
+        hit, mask = self.empty(rn, dn), self.empty(rn, dtype=torch.uint8)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_visibility_rays(alpha.data_ptr(), nvalid.data_ptr(), rn, dn, int(ray_mask_view_num),
+                                                    int(ray_mask_point_num), hit.data_ptr(), mask.data_ptr(), s))
+        self._event_done(ev, 'vis_rays', rn * dn)
+        return {'hit_prob': hit, 'alpha': alpha, 'ray_mask': mask.bool(), 'nvalid': nvalid}
+
     def direct_render_rays_backward(self, alpha, colors, d_pixel, d_hit_prob=None):
         """Backward of direct_render's ray kernel: alpha [rn,dn] (logits), colors [rn,dn,3] (the SH colours), d_pixel [rn,3], d_hit_prob
         [rn,dn] or None -> (d_alpha [rn,dn], d_colors [rn,dn,3])"""

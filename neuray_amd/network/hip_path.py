@@ -6,7 +6,9 @@ methods can be grafted onto an already constructed reference instance (neuray_am
 by the mirror classes of network/renderer.py.
 
 Replaced reference methods (same signatures): `render_by_depth` (renderer.py:168-203), `fine_render_impl` (:205-215),
-`render_impl` (:217-226), `predict_self_hit_prob` (:147-155).  Under autograd each pass is a torch.autograd.Function
+`render_impl` (:217-226), `predict_self_hit_prob` (:147-155).  cfg['hip_coarse_pass'] = 'visibility' (not a reference key; the
+environment variable NEURAY_HIP_COARSE wins) replaces the coarse network pass by the visibility estimate of the input views
+(`_visibility_coarse`): inference only, the fine pass is the only one that renders colours.  Under autograd each pass is a torch.autograd.Function
 whose backward runs the backward kernels (network/autograd.py).  Anything the HIP path does not implement raises - it
 never silently switches to an eager implementation.
 """
@@ -18,7 +20,7 @@ from ..engine import RenderEngine
 from .autograd import DirectRenderFn, PassRun, RenderPassFn, RenderPassSelfFn, SelfHitFn
 
 HOT_PATH_METHODS = ('engine', '_packed_pass', '_same_tensors', '_views', '_query', '_self_hit_prob', '_direct_rendering',
-                    'render_by_depth', 'predict_self_hit_prob', 'fine_render_impl', 'render_impl')
+                    '_coarse_pass_mode', '_visibility_coarse', 'render_by_depth', 'predict_self_hit_prob', 'fine_render_impl', 'render_impl')
 
 
 class HipRenderPath:
@@ -189,6 +191,53 @@ class HipRenderPath:
         vis = vis if dec.cfg['use_vis'] else None
         return eng.self_hit_prob(qconst, que_depth[0], mean, var, aw, vis)[None]
 
+    def _coarse_pass_mode(self):
+        """'network' (the reference's algorithm: the aggregation network on the coarse samples) or 'visibility'; the environment wins
+        over cfg['hip_coarse_pass'], as NEURAY_HIP_ARITH does over cfg['hip_arith'].  What 'visibility' cannot serve is refused here,
+        before anything is launched."""
+        mode = os.environ.get('NEURAY_HIP_COARSE') or self.cfg.get('hip_coarse_pass', 'network')
+        if mode not in ('network', 'visibility'):
+            raise ValueError("neuray_amd: coarse pass %r (cfg['hip_coarse_pass'] / NEURAY_HIP_COARSE: 'network' or 'visibility')" % (mode,))
+        if mode == 'network':
+            return mode
+        cfg = self.cfg
+        if not cfg['use_hierarchical_sampling']:
+            raise ValueError("neuray_amd: cfg['hip_coarse_pass'] = 'visibility' needs use_hierarchical_sampling: the visibility pass "
+                             "renders no colours, so without the fine pass there is no pass left that does")
+        if cfg.get('use_dr_prediction', False):
+            raise NotImplementedError("neuray_amd: cfg['hip_coarse_pass'] = 'visibility' with use_dr_prediction is not built (direct rendering "
+                                      "reads the per-view record of a network pass); use 'network'")
+        if cfg.get('hip_variant', 'fp32') != 'fp32':
+            raise NotImplementedError("neuray_amd: cfg['hip_coarse_pass'] = 'visibility' lives in the fp32 library (hip_variant = %r)"
+                                      % (cfg.get('hip_variant'),))
+        return mode
+
+    def _visibility_coarse(self, que_depth, que_imgs_info, ref_imgs_info):
+        """The coarse pass of cfg['hip_coarse_pass'] = 'visibility': hit probabilities of the coarse samples from the input views'
+        visibility alone (predict_alpha_values_dr + decode_alpha_value + alpha_values2hit_prob, renderer.py:85-94,121-123) with the COARSE
+        dist decoder - no aggregation network, no colours.  -> {'hit_prob_dr', 'ray_mask'?, 'pixel_colors_gt'?}"""
+        cfg = self.cfg
+        coords = que_imgs_info['coords']
+        assert coords.shape[0] == 1 and que_depth.shape[0] == 1, "one query view per call (qn = 1)"
+        dist = self.dist_decoder
+        diff = list(dist.parameters()) + list(self.agg_net.parameters()) + list(self.fine_dist_decoder.parameters()) + \
+            list(self.fine_agg_net.parameters()) + [ref_imgs_info['ray_feats'], ref_imgs_info['img_feats']]
+        if torch.is_grad_enabled() and any(t.requires_grad for t in diff):
+            raise NotImplementedError("neuray_amd: cfg['hip_coarse_pass'] = 'visibility' is inference only (the visibility kernels have no "
+                                      "backward); render under torch.no_grad() or train with 'network'")
+        eng = self.engine(coords.device)
+        views = self._views(eng, ref_imgs_info)
+        qconst = self._query(eng, que_imgs_info)
+        res = eng.visibility_pass(qconst, views, coords[0].contiguous(), que_depth[0].detach().contiguous(), self._packed_pass(eng, False),
+                                  use_vis=dist.cfg['use_vis'], var_bias=dist.cfg['bias_val'], ground=float(cfg['alpha_value_ground_state']),
+                                  ray_mask_view_num=cfg['ray_mask_view_num'], ray_mask_point_num=cfg['ray_mask_point_num'])
+        outputs = {'hit_prob_dr': res['hit_prob'][None]}
+        if 'imgs' in que_imgs_info:
+            outputs['pixel_colors_gt'] = eng.interpolate_feats(que_imgs_info['imgs'], coords, align_corners=True)
+        if cfg['use_ray_mask']:
+            outputs['ray_mask'] = res['ray_mask'][None]
+        return outputs
+
     def fine_render_impl(self, coarse_render_info, que_imgs_info, ref_imgs_info, is_train):
         """network/renderer.py:205-215"""
         depth, hit = coarse_render_info['depth'], coarse_render_info['hit_prob']
@@ -219,6 +268,7 @@ class HipRenderPath:
                 sub['_neuray_fine_range'] = que_imgs_info['depth_range'][0:1]
                 outs.append(self.render_impl(sub, ref_imgs_info, is_train))
             return {k: torch.cat([o[k] for o in outs], 0) for k in outs[0]}
+        visibility = self._coarse_pass_mode() == 'visibility'
         eng = self.engine(coords.device)
         rn = coords.shape[1]
         # the fine-sampling uniforms (render_ops.py:205: torch.rand on the CPU generator, the only draw of render_impl) are taken
@@ -230,9 +280,12 @@ class HipRenderPath:
         if hook is not None:
             hook()
         que_depth = eng.sample_coarse_depth(que_imgs_info['depth_range'], rn, self.cfg['depth_sample_num'])[None]
-        outputs = self.render_by_depth(que_depth, que_imgs_info, ref_imgs_info, is_train, False)
+        if visibility:       # (no 'pixel_colors_nr': the fine pass is the only one that renders colours)
+            outputs = self._visibility_coarse(que_depth, que_imgs_info, ref_imgs_info)
+        else:
+            outputs = self.render_by_depth(que_depth, que_imgs_info, ref_imgs_info, is_train, False)
         if self.cfg['use_hierarchical_sampling']:
-            coarse = {'depth': que_depth, 'hit_prob': outputs['hit_prob_nr'], '_neuray_u': u}
+            coarse = {'depth': que_depth, 'hit_prob': outputs['hit_prob_dr' if visibility else 'hit_prob_nr'], '_neuray_u': u}
             for k, v in self.fine_render_impl(coarse, que_imgs_info, ref_imgs_info, is_train).items():
                 outputs[k + '_fine'] = v
         return outputs

@@ -47,6 +47,11 @@ class NeuralRayBaseRenderer(HipRenderPath, nn.Module):
         # 'x3' = every operand split exactly into three bf16 parts on the K = 32 bf16 MFMA, six products per K = 32 with fp32
         # accumulation - each product within 2^-23 of exact (NeurayPointsArgs.arith).  Training always 'f32'.
         'hip_arith': 'f32',
+        # not a reference key: 'network' = the reference's coarse pass (the aggregation network on the coarse samples); 'visibility' = the
+        # coarse hit probabilities from the input views' visibility alone (renderer.py:85-94,121-123: the hit_prob_dr estimate) - the
+        # network runs on the fine samples only, there is no 'pixel_colors_nr'.  Inference only, needs use_hierarchical_sampling
+        # (DESIGN.md section 4.17).  The environment variable NEURAY_HIP_COARSE wins.
+        'hip_coarse_pass': 'network',
         # not a reference key: the inference packs carry prob_embed.2 folded into its consumers neuray_fc.0 / base_fc.0 (one 32 x 32
         # layer less per (point, view); the same function up to fp32 rounding - neuray_pack_pass_weights_folded)
         'hip_fold_prob_embed': True,
