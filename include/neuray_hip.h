@@ -623,6 +623,58 @@ int neuray_visibility_points(const NeurayVisibilityArgs* args, void* stream);
 int neuray_visibility_rays(const float* alpha_dev, const int* nvalid_dev, int rn, int dn, int view_num, int point_num, float* hit_prob_dev,
                            unsigned char* ray_mask_dev, void* stream);
 
+/* ---- the deterministic training backward (cfg['hip_deterministic'], NEURAY_HIP_DETERMINISTIC; added within ABI 11:
+ * every entry point and struct above is unchanged).  The same backward kernels without float atomics: every workgroup stores its sums to
+ * its own row of a partials buffer, and the rows are added in ascending workgroup order (neuray_reduce_partials: out[k] += p[0][k] +
+ * p[1][k] + ... + p[g-1][k], plain fp32 adds); the maps' gradients are a segmented sum over STABLY sorted (texel, column, tap) keys - the
+ * caller sorts (e.g. torch.sort(stable=True)) between the two calls and passes the sorted keys and the permutation.  For one library, one
+ * device model and identical inputs the results are bitwise reproducible; they are not bitwise those of the atomic entry points.
+ * neuray_deterministic_partials_floats(kernel, rn, dn): floats of the partials buffer of a NEURAY_DET_* kernel (ROWS: rn = rows, dn unused).
+ * The *_det entries take the arguments of their namesakes plus the scratch; buffers named `zeroed` must be zero on entry. */
+#define NEURAY_DET_POINTS 0
+#define NEURAY_DET_RAYS 1
+#define NEURAY_DET_SELF_HIT 2
+#define NEURAY_DET_ROWS 3
+size_t neuray_deterministic_partials_floats(int kernel, int rn, int dn);
+int neuray_reduce_partials(const float* partials_dev /*[g][n]*/, int g, long long n, float* out_dev /*[n], accumulated*/, void* stream);
+int neuray_render_rays_backward_det(const NeurayRaysBwdArgs* args, float* partials_dev, void* stream);
+/* The point backward: d_flat as above; the maps' gradients are NOT written by this call (args' d_ray_feats / d_img_feats are not read):
+ * it leaves rows_dev [columns][72] (column = point * 8 + view: d f_ray (32), d f_img (32), tap offsets (4), masked tap weights (4)) and
+ * keys_dev [columns][4] (view * fh * fw + texel; rfn * fh * fw for a skipped tap), columns = neuray_points_backward_scatter_columns(rn * dn).
+ * neuray_points_backward_scatter then takes the keys stably sorted and the permutation (int64: sorted position -> column * 4 + tap) and
+ * adds, one wave per texel and in ascending (column, tap) order, acc += w * g per channel, then d_map += acc. */
+long long neuray_points_backward_scatter_columns(int npoints);
+int neuray_render_points_backward_det(const NeurayPointsBwdArgs* args, float* partials_zeroed_dev, float* rows_dev, int* keys_dev, void* stream);
+int neuray_points_backward_scatter(const int* sorted_keys_dev, const long long* perm_dev, const float* rows_dev, long long columns, int rfn,
+                                   int fh, int fw, float* d_ray_feats_nhwc_dev, float* d_img_feats_nhwc_dev, void* stream);
+int neuray_self_hit_prob_backward_det(const float* query_const_dev, const float* depth_dev, const float* feats_dev,
+                                      const float* packed_weights_dev, const float* packed_t_weights_dev, int has_vis_head, int use_vis,
+                                      float var_bias, const float* d_hit_dev, int rn, int dn, float* d_feats_dev, float* d_flat_weights_dev,
+                                      float* partials_zeroed_dev, void* stream);
+int neuray_dist_decoder_rows_backward_det(const float* feats_dev, const float* packed_weights_dev, const float* packed_t_dev, int n,
+                                          int has_vis_head, float var_bias, const float* d_mean_dev, const float* d_var_dev,
+                                          const float* d_aw_dev, const float* d_vis_dev, float* d_feats_dev, float* d_flat_dev,
+                                          float* partials_zeroed_dev, void* stream);
+/* neuray_interpolate_feats_backward in two steps: keys_dev [b*n][4] (image * fh * fw + texel; b * fh * fw where the tap is skipped: mask 0
+ * or weight 0) and wts_dev [b*n][4]; after the stable sort, d_feats [b][c][fh][fw] += sum in ascending (point, tap) order of
+ * w * (d_out * mask). */
+int neuray_interpolate_scatter_keys(const float* points_dev, const float* mask_dev, int b, int n, int fh, int fw, int h_full, int w_full,
+                                    int align_corners, int* keys_dev, float* wts_dev, void* stream);
+int neuray_interpolate_feats_backward_sorted(const float* d_out_dev, const float* mask_dev, const int* sorted_keys_dev,
+                                             const long long* perm_dev, const float* wts_dev, int b, int n, int c, int fh, int fw,
+                                             float* d_feats_dev, void* stream);
+/* The fused InstanceNorm with ordered statistics: partials_dev [n*c][neuray_inorm_chunks(n, c, h, w)][2] receives every workgroup's pair of
+ * sums, raw_dev [n*c][2] their sum in workgroup order (neither needs zeroing); everything else as neuray_inorm_forward / _backward. */
+int neuray_inorm_chunks(int n, int c, int h, int w);
+int neuray_inorm_forward_det(const float* x_dev, const float* gamma_dev, const float* beta_dev, const float* res_dev, long long res_stride_n,
+                             long long res_stride_c, long long res_stride_h, int n, int c, int h, int w, int pad, int act, float eps,
+                             float* partials_dev, float* raw_dev, float* stats_dev, float* out_padded_dev, long long out_stride_n,
+                             void* stream);
+int neuray_inorm_backward_det(const float* x_dev, const float* out_padded_dev, long long out_stride_n, const float* d_out_padded_dev,
+                              long long d_out_stride_n, const float* stats_dev, const float* gamma_dev, int n, int c, int h, int w, int pad,
+                              int act, float* partials_dev, float* raw_dev, float* dx_dev, float* d_res_dev, float* d_gamma_dev,
+                              float* d_beta_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,7 @@ class NeurayVisibilityArgs(C.Structure):
 
 LOSS_RENDER, LOSS_CONSIST, LOSS_DEPTH = 0, 1, 2   # NeurayLossTerm.kind (include/neuray_hip.h NEURAY_LOSS_*)
 LOSS_MAX_TERMS = 4
+DET_POINTS, DET_RAYS, DET_SELF_HIT, DET_ROWS = 0, 1, 2, 3   # neuray_deterministic_partials_floats (include/neuray_hip.h NEURAY_DET_*)
 
 PACKED_RAY_FLOATS = 1348
 RAY_ATT_SAVE = 24            # NEURAY_RAY_ATT_SAVE
@@ -212,6 +213,23 @@ SYMBOLS = {
     'neuray_train_loss_backward': (C.c_int, [C.POINTER(NeurayTrainLossArgs), C.c_void_p]),
     'neuray_visibility_points': (C.c_int, [C.POINTER(NeurayVisibilityArgs), C.c_void_p]),
     'neuray_visibility_rays': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the deterministic training backward
+    'neuray_deterministic_partials_floats': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'neuray_reduce_partials': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
+    'neuray_render_rays_backward_det': (C.c_int, [C.POINTER(NeurayRaysBwdArgs), C.c_void_p, C.c_void_p]),
+    'neuray_points_backward_scatter_columns': (C.c_longlong, [C.c_int]),
+    'neuray_render_points_backward_det': (C.c_int, [C.POINTER(NeurayPointsBwdArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'neuray_points_backward_scatter': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+    'neuray_self_hit_prob_backward_det': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                                    C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'neuray_dist_decoder_rows_backward_det': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'neuray_interpolate_scatter_keys': (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 3),
+    'neuray_interpolate_feats_backward_sorted': (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 2),
+    'neuray_inorm_chunks': (C.c_int, [C.c_int] * 4),
+    'neuray_inorm_forward_det': (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] * 3 + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p]),
+    'neuray_inorm_backward_det': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 7),
 }
 
 

@@ -594,7 +594,7 @@ int neuray_inorm_forward(const float* x, const float* gamma, const float* beta, 
     const long long img = (long long)c * (h + 2 * pad) * (w + 2 * pad);
     if (out_stride_n != 0 && out_stride_n < img) return fail("neuray_inorm_forward: out_stride_n %lld < %lld", out_stride_n, img);
     const int planes = n * c, hw = h * w;
-    NR_LAUNCH(nr::inorm_stats_kernel, dim3(norm_chunks(planes, hw), planes), dim3(256), 0, stream, x, hw, raw_zeroed);
+    NR_LAUNCH(nr::inorm_stats_kernel<false>, dim3(norm_chunks(planes, hw), planes), dim3(256), 0, stream, x, hw, raw_zeroed);
     nr::NormApplyParams p;
     p.x = x; p.raw = raw_zeroed; p.gamma = gamma; p.beta = beta; p.res = res; p.out = out_padded; p.stats = stats;
     p.rs_n = res_stride_n; p.rs_c = res_stride_c; p.rs_h = res_stride_h; p.out_stride_n = out_stride_n ? out_stride_n : img;
@@ -618,7 +618,7 @@ int neuray_inorm_backward(const float* x, const float* out_padded, long long out
     p.out_stride_n = out_stride_n ? out_stride_n : img; p.d_out_stride_n = d_out_stride_n ? d_out_stride_n : img;
     p.n = n; p.c = c; p.h = h; p.w = w; p.pad = pad; p.act = act;
     const int planes = n * c, hw = h * w;
-    NR_LAUNCH(nr::inorm_backward_reduce_kernel, dim3(norm_chunks(planes, hw), planes), dim3(256), 0, stream, p);
+    NR_LAUNCH(nr::inorm_backward_reduce_kernel<false>, dim3(norm_chunks(planes, hw), planes), dim3(256), 0, stream, p);
     NR_LAUNCH(nr::inorm_backward_apply_kernel, dim3(norm_chunks(planes, hw), planes), dim3(256), 0, stream, p);
     return check_launch("neuray_inorm_backward");
 }
@@ -944,6 +944,244 @@ int neuray_interpolate_feats_backward_staged(const float* d_out, const float* po
     if (int rc = check_launch("neuray_interpolate_feats_backward_staged")) return rc;
     NR_LAUNCH(nr::nhwc_add_to_nchw_kernel, dim3((fh * fw + 31) / 32, ((c + 31) / 32) * b), dim3(256), 0, stream, tmp_nhwc_zeroed, fh * fw, c, d_feats);
     return check_launch("neuray_interpolate_feats_backward_staged");
+}
+
+// ---- the deterministic training backward (cfg['hip_deterministic']): the same kernels instantiated with DET = true - plain
+// stores of every workgroup's sums to a partials buffer - and the ordered reductions of nr_kernels_bwd.h.  No float atomics on this path.
+namespace {
+int rays_bwd_grid(int rn, int dn) { return grid_for(rn, nr::ray_bwd_waves(dn), 256 * 4); }
+int reduce_partials(const float* partials, int g, long long n, float* out, void* stream) {
+    NR_LAUNCH(nr::reduce_partials_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, partials, g, n, out);
+    return check_launch("neuray_reduce_partials");
+}
+int scatter_sorted(const nr::ScatterSortedParams& p, void* stream) {
+    NR_LAUNCH(nr::scatter_sorted_kernel, dim3(grid_for(p.ntex, 4, 256 * 16)), dim3(256), 0, stream, p);
+    return check_launch("scatter_sorted");
+}
+}  // namespace
+
+size_t neuray_deterministic_partials_floats(int kernel, int rn, int dn) {
+    if (rn < 1) return 0;
+    switch (kernel) {
+        case NEURAY_DET_RAYS: return dn < 1 ? 0 : (size_t)rays_bwd_grid(rn, dn) * nr::kPackedRayFloats;
+#ifndef NR_INFERENCE_ONLY
+        case NEURAY_DET_POINTS: return dn < 1 ? 0 : (size_t)2 * grid_for((long long)rn * dn, 16, 256) * nr::kFlatPassFloats;
+        case NEURAY_DET_SELF_HIT: case NEURAY_DET_ROWS: return (size_t)grid_for(rn, 16, 512) * nr::kFlatPassFloats;
+#endif
+        default: return 0;
+    }
+}
+
+int neuray_reduce_partials(const float* partials_dev, int g, long long n, float* out_dev, void* stream) {
+    if (!partials_dev || !out_dev) return fail("neuray_reduce_partials: null argument");
+    if (g < 1 || n < 1) return fail("neuray_reduce_partials: g=%d n=%lld", g, n);
+    return reduce_partials(partials_dev, g, n, out_dev, stream);
+}
+
+int neuray_render_rays_backward_det(const NeurayRaysBwdArgs* a, float* partials_dev, void* stream) {
+    if (!a || !a->point_rec_dev || !a->depth_dev || !a->pos_enc_dev || !a->packed_weights_dev || !a->d_pixel_dev ||
+        !a->d_point_rec_dev || !a->d_ray_weights_dev || !partials_dev)
+        return fail("neuray_render_rays_backward_det: null argument");
+    if (a->rn < 1) return fail("neuray_render_rays_backward_det: rn=%d", a->rn);
+    if (a->dn < 3 || a->dn > NEURAY_MAX_SAMPLES) return fail("neuray_render_rays_backward_det: dn=%d outside [3,%d]", a->dn, NEURAY_MAX_SAMPLES);
+    nr::RayBwdParams p;
+    p.point_rec = a->point_rec_dev; p.depth = a->depth_dev; p.pos_enc = a->pos_enc_dev; p.weights = a->packed_weights_dev;
+    p.d_pixel = a->d_pixel_dev; p.d_hit_prob = a->d_hit_prob_dev; p.d_depth = a->d_render_depth_dev;
+    p.d_point_rec = a->d_point_rec_dev; p.d_weights = partials_dev; p.att_saved = a->att_saved_dev; p.rn = a->rn; p.dn = a->dn;
+    const size_t smem = nr::ray_bwd_smem_bytes(a->dn, true);
+    const int waves = nr::ray_bwd_waves(a->dn);
+    const int grid = rays_bwd_grid(a->rn, a->dn);
+    if (a->dn <= 64) {
+        auto k = nr::rays_backward_kernel<1, true>;
+#ifndef NEURAY_EMU
+        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+#endif
+        NR_LAUNCH(k, dim3(grid), dim3(64 * waves), smem, stream, p);
+    } else {
+        auto k = nr::rays_backward_kernel<2, true>;
+#ifndef NEURAY_EMU
+        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+#endif
+        NR_LAUNCH(k, dim3(grid), dim3(64 * waves), smem, stream, p);
+    }
+    if (int rc = check_launch("neuray_render_rays_backward_det")) return rc;
+    return reduce_partials(partials_dev, grid, nr::kPackedRayFloats, a->d_ray_weights_dev, stream);
+}
+
+long long neuray_points_backward_scatter_columns(int npoints) {
+#ifdef NR_INFERENCE_ONLY
+    (void)npoints;
+    return 0;
+#else
+    return npoints < 1 ? 0 : (long long)((npoints + 15) / 16) * 16 * nr::kB2Waves;
+#endif
+}
+
+int neuray_render_points_backward_det(const NeurayPointsBwdArgs* a, float* partials_zeroed_dev, float* rows_dev, int* keys_dev, void* stream) {
+    if (!a || !a->query_const_dev || !a->view_const_dev || !a->coords_dev || !a->depth_dev || !a->ray_feats_nhwc_dev ||
+        !a->img_feats_nhwc_dev || !a->rgba_dev || !a->flat_weights_dev || !a->d_point_rec_dev || !a->d_flat_weights_dev ||
+        !partials_zeroed_dev || !rows_dev || !keys_dev)
+        return fail("neuray_render_points_backward_det: null argument");
+    if (a->rfn < 1 || a->rfn > NEURAY_MAX_VIEWS) return fail("neuray_render_points_backward_det: rfn=%d outside [1,%d]", a->rfn, NEURAY_MAX_VIEWS);
+    if (a->rn < 1 || a->dn < 3 || a->dn > NEURAY_MAX_SAMPLES) return fail("neuray_render_points_backward_det: rn=%d dn=%d", a->rn, a->dn);
+#ifdef NR_INFERENCE_ONLY
+    return fail("neuray_render_points_backward_det: the bf16-operand library is inference only");
+#else
+    if (a->rfn > nr::kB2Waves)
+        return fail("neuray_render_points_backward_det: rfn=%d - the backward covers at most %d reference views", a->rfn, nr::kB2Waves);
+    if ((long long)(a->rfn + 1) * a->fh * a->fw > 0x7fffffffLL) return fail("neuray_render_points_backward_det: the maps' texels do not fit a 32-bit sort key");
+    if (!a->packed_weights_dev || !a->packed_t_weights_dev || !a->saved_dev || !a->handover_dev)
+        return fail("neuray_render_points_backward_det: packed_weights_dev, packed_t_weights_dev, saved_dev and handover_dev are needed (as neuray_render_points_backward)");
+    nr::PointBwd2Params q;
+    q.que_const = a->query_const_dev; q.view_const = a->view_const_dev; q.coords = a->coords_dev; q.depth = a->depth_dev;
+    q.ray_feats = a->ray_feats_nhwc_dev; q.img_feats = a->img_feats_nhwc_dev; q.rgba = a->rgba_dev;
+    q.weights = a->packed_weights_dev; q.weights_t = a->packed_t_weights_dev;
+    q.d_point_rec = a->d_point_rec_dev; q.saved = a->saved_dev;
+    q.d_ray_feats = rows_dev; q.d_img_feats = reinterpret_cast<float*>(keys_dev);       // (the DET instantiation's meaning of the two fields)
+    q.rfn = a->rfn; q.rn = a->rn; q.dn = a->dn; q.h = a->h; q.w = a->w; q.fh = a->fh; q.fw = a->fw;
+    q.use_vis = a->use_vis; q.var_bias = a->var_bias;
+    q.handover = a->handover_dev;
+    const int grid2 = grid_for((long long)a->rn * a->dn, 16, 256);
+    const size_t smem = nr::point_bwd2_smem_bytes();
+    auto launch = [&](auto k, float* partials) {
+        q.d_flat = partials;
+#ifndef NEURAY_EMU
+        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+#endif
+        NR_LAUNCH(k, dim3(grid2), dim3(64 * nr::kB2Waves), smem, stream, q);
+    };
+    float* p_tail = partials_zeroed_dev;
+    float* p_front = partials_zeroed_dev + (size_t)grid2 * nr::kFlatPassFloats;
+    const bool vis = a->has_vis_head && a->use_vis;
+    if (vis) { launch(nr::points_backward2_kernel<true, nr::B2_TAIL, true>, p_tail); launch(nr::points_backward2_kernel<true, nr::B2_FRONT, true>, p_front); }
+    else { launch(nr::points_backward2_kernel<false, nr::B2_TAIL, true>, p_tail); launch(nr::points_backward2_kernel<false, nr::B2_FRONT, true>, p_front); }
+    if (int rc = check_launch("neuray_render_points_backward_det")) return rc;
+    // each half has its own reduce launch, in stream order: tail's rows first, then front's
+    if (int rc = reduce_partials(p_tail, grid2, nr::kFlatPassFloats, a->d_flat_weights_dev, stream)) return rc;
+    return reduce_partials(p_front, grid2, nr::kFlatPassFloats, a->d_flat_weights_dev, stream);
+#endif
+}
+
+int neuray_points_backward_scatter(const int* sorted_keys_dev, const long long* perm_dev, const float* rows_dev, long long columns, int rfn,
+                                   int fh, int fw, float* d_ray_feats_nhwc_dev, float* d_img_feats_nhwc_dev, void* stream) {
+#ifdef NR_INFERENCE_ONLY
+    return fail("neuray_points_backward_scatter: the bf16-operand library is inference only");
+#else
+    if (!sorted_keys_dev || !perm_dev || !rows_dev || !d_ray_feats_nhwc_dev || !d_img_feats_nhwc_dev) return fail("neuray_points_backward_scatter: null argument");
+    if (columns < 1 || rfn < 1 || rfn > nr::kB2Waves || fh < 1 || fw < 1 || (long long)(rfn + 1) * fh * fw > 0x7fffffffLL)
+        return fail("neuray_points_backward_scatter: bad shape");
+    nr::ScatterSortedParams p;
+    p.keys = sorted_keys_dev; p.perm = perm_dev; p.g = rows_dev; p.wts = rows_dev + 68; p.mask = nullptr;
+    p.out0 = d_ray_feats_nhwc_dev; p.out1 = d_img_feats_nhwc_dev;
+    p.m = columns * 4; p.img_stride = (long long)fh * fw * 32; p.tex_stride = 32; p.ch_stride = 1;
+    p.ntex = rfn * fh * fw; p.hw = fh * fw; p.c = 64; p.split = 32; p.g_stride = nr::kB2ScatterRow; p.w_stride = nr::kB2ScatterRow;
+    return scatter_sorted(p, stream);
+#endif
+}
+
+int neuray_self_hit_prob_backward_det(const float* qc, const float* depth, const float* feats, const float* packed, const float* packed_t,
+                                      int has_vis_head, int use_vis, float var_bias, const float* d_hit, int rn, int dn,
+                                      float* d_feats, float* d_flat, float* partials_zeroed_dev, void* stream) {
+#ifdef NR_INFERENCE_ONLY
+    return fail("neuray_self_hit_prob_backward_det: the bf16-operand variant is inference only");
+#else
+    if (!qc || !depth || !feats || !packed || !packed_t || !d_hit || !d_feats || !d_flat || !partials_zeroed_dev)
+        return fail("neuray_self_hit_prob_backward_det: null argument");
+    if (rn < 1 || dn < 3 || dn > NEURAY_MAX_SAMPLES) return fail("neuray_self_hit_prob_backward_det: rn=%d dn=%d", rn, dn);
+    nr::SelfHitBwd2Params p;
+    p.que_const = qc; p.depth = depth; p.feats = feats; p.weights = packed; p.weights_t = packed_t; p.d_hit = d_hit;
+    p.d_feats = d_feats; p.d_flat = partials_zeroed_dev; p.rn = rn; p.dn = dn; p.use_vis = use_vis; p.var_bias = var_bias;
+    const int g = grid_for(rn, 16, 512);
+    if (has_vis_head && use_vis) { auto k = nr::self_hit_backward2_kernel<true, true>; NR_LAUNCH(k, dim3(g), dim3(64), 0, stream, p); }
+    else { auto k = nr::self_hit_backward2_kernel<false, true>; NR_LAUNCH(k, dim3(g), dim3(64), 0, stream, p); }
+    if (int rc = check_launch("neuray_self_hit_prob_backward_det")) return rc;
+    return reduce_partials(partials_zeroed_dev, g, nr::kFlatPassFloats, d_flat, stream);
+#endif
+}
+
+int neuray_dist_decoder_rows_backward_det(const float* feats, const float* packed, const float* packed_t, int n, int has_vis_head,
+                                          float var_bias, const float* d_mean, const float* d_var, const float* d_aw, const float* d_vis,
+                                          float* d_feats, float* d_flat, float* partials_zeroed_dev, void* stream) {
+#ifdef NR_INFERENCE_ONLY
+    return fail("neuray_dist_decoder_rows_backward_det: the bf16-operand variant is inference only");
+#else
+    if (!feats || !packed || !packed_t || !d_feats || !d_flat || !partials_zeroed_dev) return fail("neuray_dist_decoder_rows_backward_det: null argument");
+    if (n < 1) return fail("neuray_dist_decoder_rows_backward_det: n=%d", n);
+    nr::RowsBwd2Params p;
+    p.feats = feats; p.weights = packed; p.weights_t = packed_t; p.d_mean = d_mean; p.d_var = d_var; p.d_aw = d_aw; p.d_vis = d_vis;
+    p.d_feats = d_feats; p.d_flat = partials_zeroed_dev; p.n = n; p.var_bias = var_bias;
+    const int g = grid_for(n, 16, 512);
+    if (has_vis_head && d_vis) { auto k = nr::decoder_rows_backward2_kernel<true, true>; NR_LAUNCH(k, dim3(g), dim3(64), 0, stream, p); }
+    else { auto k = nr::decoder_rows_backward2_kernel<false, true>; NR_LAUNCH(k, dim3(g), dim3(64), 0, stream, p); }
+    if (int rc = check_launch("neuray_dist_decoder_rows_backward_det")) return rc;
+    return reduce_partials(partials_zeroed_dev, g, nr::kFlatPassFloats, d_flat, stream);
+#endif
+}
+
+int neuray_interpolate_scatter_keys(const float* points, const float* mask, int b, int n, int fh, int fw, int h_full, int w_full,
+                                    int align_corners, int* keys_dev, float* wts_dev, void* stream) {
+    if (!points || !keys_dev || !wts_dev) return fail("neuray_interpolate_scatter_keys: null argument");
+    if (b < 1 || n < 1 || fh < 1 || fw < 1 || (long long)(b + 1) * fh * fw > 0x7fffffffLL) return fail("neuray_interpolate_scatter_keys: bad shape");
+    NR_LAUNCH(nr::interpolate_scatter_keys_kernel, dim3(grid_for((long long)b * n, 256, 4096)), dim3(256), 0, stream, points, mask, b, n, fh,
+              fw, h_full, w_full, align_corners, keys_dev, wts_dev);
+    return check_launch("neuray_interpolate_scatter_keys");
+}
+
+int neuray_interpolate_feats_backward_sorted(const float* d_out, const float* mask, const int* sorted_keys_dev, const long long* perm_dev,
+                                             const float* wts_dev, int b, int n, int c, int fh, int fw, float* d_feats, void* stream) {
+    if (!d_out || !sorted_keys_dev || !perm_dev || !wts_dev || !d_feats) return fail("neuray_interpolate_feats_backward_sorted: null argument");
+    if (b < 1 || n < 1 || c < 1 || fh < 1 || fw < 1 || (long long)(b + 1) * fh * fw > 0x7fffffffLL) return fail("neuray_interpolate_feats_backward_sorted: bad shape");
+    nr::ScatterSortedParams p;
+    p.keys = sorted_keys_dev; p.perm = perm_dev; p.g = d_out; p.wts = wts_dev; p.mask = mask; p.out0 = d_feats; p.out1 = d_feats;
+    p.m = (long long)b * n * 4; p.img_stride = (long long)c * fh * fw; p.tex_stride = 1; p.ch_stride = (long long)fh * fw;
+    p.ntex = b * fh * fw; p.hw = fh * fw; p.c = c; p.split = c; p.g_stride = c; p.w_stride = 4;
+    return scatter_sorted(p, stream);
+}
+
+int neuray_inorm_chunks(int n, int c, int h, int w) {
+    if (n < 1 || c < 1 || h < 1 || w < 1) return 0;
+    return norm_chunks(n * c, h * w);
+}
+
+int neuray_inorm_forward_det(const float* x, const float* gamma, const float* beta, const float* res, long long res_stride_n,
+                             long long res_stride_c, long long res_stride_h, int n, int c, int h, int w, int pad, int act, float eps,
+                             float* partials, float* raw, float* stats, float* out_padded, long long out_stride_n, void* stream) {
+    if (!x || !gamma || !beta || !partials || !raw || !stats || !out_padded) return fail("neuray_inorm_forward_det: null pointer");
+    if (n < 1 || c < 1 || h < 1 || w < 1 || pad < 0 || pad >= h || pad >= w || act < 0 || act > 2 || (long long)(h + 2 * pad) * (w + 2 * pad) >= (1 << 23))
+        return fail("neuray_inorm_forward_det: bad arguments n=%d c=%d h=%d w=%d pad=%d act=%d", n, c, h, w, pad, act);
+    const long long img = (long long)c * (h + 2 * pad) * (w + 2 * pad);
+    if (out_stride_n != 0 && out_stride_n < img) return fail("neuray_inorm_forward_det: out_stride_n %lld < %lld", out_stride_n, img);
+    const int planes = n * c, hw = h * w, chunks = norm_chunks(planes, hw);
+    NR_LAUNCH(nr::inorm_stats_kernel<true>, dim3(chunks, planes), dim3(256), 0, stream, x, hw, partials);
+    NR_LAUNCH(nr::inorm_finish_kernel, dim3((2 * planes + 255) / 256), dim3(256), 0, stream, (const float*)partials, planes, chunks, raw);
+    nr::NormApplyParams p;
+    p.x = x; p.raw = raw; p.gamma = gamma; p.beta = beta; p.res = res; p.out = out_padded; p.stats = stats;
+    p.rs_n = res_stride_n; p.rs_c = res_stride_c; p.rs_h = res_stride_h; p.out_stride_n = out_stride_n ? out_stride_n : img;
+    p.n = n; p.c = c; p.h = h; p.w = w; p.pad = pad; p.act = act; p.eps = eps;
+    NR_LAUNCH(nr::inorm_apply_kernel, dim3(norm_chunks(planes, (h + 2 * pad) * (w + 2 * pad)), planes), dim3(256), 0, stream, p);
+    return check_launch("neuray_inorm_forward_det");
+}
+
+int neuray_inorm_backward_det(const float* x, const float* out_padded, long long out_stride_n, const float* d_out_padded, long long d_out_stride_n,
+                              const float* stats, const float* gamma, int n, int c, int h, int w, int pad, int act, float* partials, float* raw,
+                              float* dx, float* d_res, float* d_gamma, float* d_beta, void* stream) {
+    if (!x || !out_padded || !d_out_padded || !stats || !gamma || !partials || !raw || !dx) return fail("neuray_inorm_backward_det: null pointer");
+    if (n < 1 || c < 1 || h < 1 || w < 1 || pad < 0 || pad >= h || pad >= w || act < 0 || act > 2 || (long long)(h + 2 * pad) * (w + 2 * pad) >= (1 << 23))
+        return fail("neuray_inorm_backward_det: bad arguments n=%d c=%d h=%d w=%d pad=%d act=%d", n, c, h, w, pad, act);
+    const long long img = (long long)c * (h + 2 * pad) * (w + 2 * pad);
+    if ((out_stride_n != 0 && out_stride_n < img) || (d_out_stride_n != 0 && d_out_stride_n < img))
+        return fail("neuray_inorm_backward_det: image strides %lld / %lld < %lld", out_stride_n, d_out_stride_n, img);
+    nr::NormBwdParams p;
+    p.x = x; p.out = out_padded; p.d_out = d_out_padded; p.stats = stats; p.gamma = gamma; p.raw = partials; p.dx = dx; p.d_res = d_res;
+    p.d_gamma = d_gamma; p.d_beta = d_beta;
+    p.out_stride_n = out_stride_n ? out_stride_n : img; p.d_out_stride_n = d_out_stride_n ? d_out_stride_n : img;
+    p.n = n; p.c = c; p.h = h; p.w = w; p.pad = pad; p.act = act;
+    const int planes = n * c, hw = h * w, chunks = norm_chunks(planes, hw);
+    NR_LAUNCH(nr::inorm_backward_reduce_kernel<true>, dim3(chunks, planes), dim3(256), 0, stream, p);
+    NR_LAUNCH(nr::inorm_finish_kernel, dim3((2 * planes + 255) / 256), dim3(256), 0, stream, (const float*)partials, planes, chunks, raw);
+    p.raw = raw;
+    NR_LAUNCH(nr::inorm_backward_apply_kernel, dim3(chunks, planes), dim3(256), 0, stream, p);
+    return check_launch("neuray_inorm_backward_det");
 }
 
 int neuray_group_sum_selftest(const float* x, float* y, void* stream) {

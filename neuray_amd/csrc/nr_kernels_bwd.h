@@ -11,6 +11,9 @@
 //       dS_ij = P_ij (do_i . v_j - D_i),  dq~_i = sum_j dS_ij k_j,  dk_j = sum_i dS_ij q~_i,  dv_j = sum_i P_ij do_i
 // Weight gradients: every per-lane contribution is summed over the wave (shuffles), then over the rays of the
 // workgroup in LDS, then added to global memory with one atomicAdd per weight and workgroup.
+// DET = true (the deterministic mode): every wave sums into an LDS accumulator of its own (plain adds: within a
+// wave each accumulator word belongs to one lane), the workgroup adds the waves' accumulators in wave order and stores the result
+// as row blockIdx.x of a partials buffer [gridDim.x][kPackedRayFloats]; reduce_partials_kernel adds the rows in workgroup order.
 #pragma once
 #include "nr_kernels.h"
 
@@ -34,13 +37,14 @@ constexpr int kRayBwdPerSample = 16 * 4 + 12 + 3;     // K, V, q~, do | shift, d
 constexpr int kRayBwdTranspose = 2 * 64 * 17;         // per wave: two [64][17] buffers of wave_outer_add
 // rays per workgroup: 4 (one sample per lane, dn <= 64) or 2 (two samples per lane, dn <= 128: the per-sample LDS state doubles)
 inline int ray_bwd_waves(int dn) { return dn <= 64 ? kRayWaves : 2; }
-inline size_t ray_bwd_smem_bytes(int dn) {
-    return sizeof(float) * (2 * (kPackedRayFloats + 12) + ray_bwd_waves(dn) * ((size_t)dn * kRayBwdPerSample + kRayBwdTranspose));
+inline size_t ray_bwd_smem_bytes(int dn, bool det = false) {      // det: one accumulator per wave (dn = 64: 143 KB, dn = 128: 112 KB of the 160)
+    return sizeof(float) * ((1 + (det ? ray_bwd_waves(dn) : 1)) * (kPackedRayFloats + 12) + ray_bwd_waves(dn) * ((size_t)dn * kRayBwdPerSample + kRayBwdTranspose));
 }
 
 // acc[o * 16 + k] += sum over the wave of a[o] * b[k]   (acc in LDS, shared by the waves of the workgroup).
 // A [16 x 64 samples] x [64 samples x 16] contraction: the per-lane vectors are transposed through LDS (tA, tB: [64][17]
 // per wave) and multiplied on the fp32 MFMA (16 K-steps of 4 samples) instead of 256 wave-wide shuffle reductions.
+template <bool DET = false>
 __device__ __forceinline__ void wave_outer_add(float* acc, const float (&a)[16], const float (&b)[16], bool act, int lane,
                                                float* tA, float* tB) {
     __syncthreads();
@@ -52,12 +56,17 @@ __device__ __forceinline__ void wave_outer_add(float* acc, const float (&a)[16],
     NR_PRAGMA_UNROLL
     for (int s = 0; s < 16; ++s) d = nr_mfma16(tA[(4 * s + kk) * 17 + m], tB[(4 * s + kk) * 17 + m], d);
     NR_PRAGMA_UNROLL
-    for (int r = 0; r < 4; ++r) atomicAdd(acc + (4 * kk + r) * 16 + m, d[r]);      // D: row o = 4 kk + r, column k = m
+    for (int r = 0; r < 4; ++r) {                                                   // D: row o = 4 kk + r, column k = m
+        if constexpr (DET) acc[(4 * kk + r) * 16 + m] += d[r];                      // (the wave's own accumulator: one lane per word)
+        else atomicAdd(acc + (4 * kk + r) * 16 + m, d[r]);
+    }
 }
+template <bool DET = false>
 __device__ __forceinline__ void wave_vec_add(float* acc, const float (&a)[16], bool act, int lane) {
     for (int o = 0; o < 16; ++o) {
         const float s = wave_sum(act ? a[o] : 0.0f);
-        if (lane == 0) atomicAdd(acc + o, s);
+        if constexpr (DET) { if (lane == 0) acc[o] += s; }
+        else { if (lane == 0) atomicAdd(acc + o, s); }
     }
 }
 // y[k] = sum_o M[o][k] x[o]   (transposed product with the row-major LDS matrix M)
@@ -83,7 +92,8 @@ struct RayBwdSample {
 };
 
 // NCH samples per lane: NCH = 1 for dn <= 64 (4 rays per workgroup), NCH = 2 for dn <= 128 (2 rays per workgroup)
-template <int NCH>
+// DET: p.d_weights is the partials buffer [gridDim.x][kPackedRayFloats] (plain stores, every word of the workgroup's row)
+template <int NCH, bool DET = false>
 __global__ void __launch_bounds__(256) rays_backward_kernel(RayBwdParams p) {
     NR_DYNAMIC_SMEM(float, smem);
     const int lane = threadIdx.x & 63;
@@ -92,12 +102,18 @@ __global__ void __launch_bounds__(256) rays_backward_kernel(RayBwdParams p) {
     const int dn = p.dn;
     float* RW = smem + nr_opaque_zero();
     float* WA = smem + kPackedRayFloats + 12;          // weight-gradient accumulators of the workgroup
-    float* base = smem + 2 * (kPackedRayFloats + 12) + (size_t)wave * (dn * kRayBwdPerSample + kRayBwdTranspose);
+    if constexpr (DET) WA += wave * (kPackedRayFloats + 12);                 // ... of this wave
+    float* base = smem + (DET ? 1 + nwaves : 2) * (kPackedRayFloats + 12) + (size_t)wave * (dn * kRayBwdPerSample + kRayBwdTranspose);
     float* ks = base; float* vs = ks + dn * 16; float* qs = vs + dn * 16; float* dos = qs + dn * 16;
     float* st = dos + dn * 16;                         // [dn][12]: softmax shift (4), 1 / denominator (4), D (4)
     float* tr = st + dn * 12; float* al = tr + dn; float* us = al + dn;
     float* tA = us + dn; float* tB = tA + 64 * 17;
-    for (int i = threadIdx.x; i < kPackedRayFloats; i += blockDim.x) { RW[i] = p.weights[kPackedPointFloats + i]; WA[i] = 0.0f; }
+    if constexpr (DET) {
+        for (int i = threadIdx.x; i < kPackedRayFloats; i += blockDim.x) RW[i] = p.weights[kPackedPointFloats + i];
+        for (int i = lane; i < kPackedRayFloats; i += 64) WA[i] = 0.0f;
+    } else {
+        for (int i = threadIdx.x; i < kPackedRayFloats; i += blockDim.x) { RW[i] = p.weights[kPackedPointFloats + i]; WA[i] = 0.0f; }
+    }
     __syncthreads();
     const int nray_iter = (p.rn + nwaves - 1) / nwaves;
 
@@ -230,11 +246,12 @@ __global__ void __launch_bounds__(256) rays_backward_kernel(RayBwdParams p) {
                 float t16[16];
                 NR_PRAGMA_UNROLL
                 for (int k = 0; k < 16; ++k) t16[k] = dsg * s.h1[k];
-                wave_vec_add(WA + RW_OG2W, t16, s.act, lane);
+                wave_vec_add<DET>(WA + RW_OG2W, t16, s.act, lane);
                 const float sb = wave_sum(s.act ? dsg : 0.0f);
-                if (lane == 0) atomicAdd(WA + RW_OG2B, sb);
-                wave_vec_add(WA + RW_OG0B, dpre1, s.act, lane);
-                wave_outer_add(WA + RW_OG0W, dpre1, s.z, s.act, lane, tA, tB);
+                if constexpr (DET) { if (lane == 0) WA[RW_OG2B] += sb; }
+                else { if (lane == 0) atomicAdd(WA + RW_OG2B, sb); }
+                wave_vec_add<DET>(WA + RW_OG0B, dpre1, s.act, lane);
+                wave_outer_add<DET>(WA + RW_OG0W, dpre1, s.z, s.act, lane, tA, tB);
             }
             matvec16_t(RW + RW_OG0W, dpre1, dz);
             // ---- LayerNorm backward
@@ -248,9 +265,9 @@ __global__ void __launch_bounds__(256) rays_backward_kernel(RayBwdParams p) {
                 float t16[16];
                 NR_PRAGMA_UNROLL
                 for (int k = 0; k < 16; ++k) t16[k] = dz[k] * s.yh[k];
-                wave_vec_add(WA + RW_LNW, t16, s.act, lane);
-                wave_vec_add(WA + RW_LNB, dz, s.act, lane);
-                wave_outer_add(WA + RW_FC, dyk[ch], s.o, s.act, lane, tA, tB);
+                wave_vec_add<DET>(WA + RW_LNW, t16, s.act, lane);
+                wave_vec_add<DET>(WA + RW_LNB, dz, s.act, lane);
+                wave_outer_add<DET>(WA + RW_FC, dyk[ch], s.o, s.act, lane, tA, tB);
             }
             matvec16_t(RW + RW_FC, dyk[ch], dO);
             // ---- attention backward, query side (this lane = query i)
@@ -302,9 +319,9 @@ __global__ void __launch_bounds__(256) rays_backward_kernel(RayBwdParams p) {
                 dk[hh * 4] = k0; dk[hh * 4 + 1] = k1; dk[hh * 4 + 2] = k2; dk[hh * 4 + 3] = k3;
                 dv[hh * 4] = v0; dv[hh * 4 + 1] = v1; dv[hh * 4 + 2] = v2; dv[hh * 4 + 3] = v3;
             }
-            wave_outer_add(WA + RW_WQ, dq[ch], s.G, s.act, lane, tA, tB);
-            wave_outer_add(WA + RW_WK, dk, s.G, s.act, lane, tA, tB);
-            wave_outer_add(WA + RW_WV, dv, s.G, s.act, lane, tA, tB);
+            wave_outer_add<DET>(WA + RW_WQ, dq[ch], s.G, s.act, lane, tA, tB);
+            wave_outer_add<DET>(WA + RW_WK, dk, s.G, s.act, lane, tA, tB);
+            wave_outer_add<DET>(WA + RW_WV, dv, s.G, s.act, lane, tA, tB);
             float gq[16], gk[16], gv[16];
             matvec16_t(RW + RW_WQ, dq[ch], gq);
             matvec16_t(RW + RW_WK, dk, gk);
@@ -321,7 +338,16 @@ __global__ void __launch_bounds__(256) rays_backward_kernel(RayBwdParams p) {
         }
         __syncthreads();
     }
-    for (int k = threadIdx.x; k < kPackedRayFloats; k += blockDim.x) atomicAdd(p.d_weights + k, WA[k]);
+    if constexpr (DET) {                               // (the loop's last barrier, or the one after the zero fill, is behind us)
+        const float* W0 = smem + kPackedRayFloats + 12;
+        for (int k = threadIdx.x; k < kPackedRayFloats; k += blockDim.x) {
+            float s = W0[k];
+            for (int w = 1; w < nwaves; ++w) s += W0[w * (kPackedRayFloats + 12) + k];
+            p.d_weights[(size_t)blockIdx.x * kPackedRayFloats + k] = s;
+        }
+    } else {
+        for (int k = threadIdx.x; k < kPackedRayFloats; k += blockDim.x) atomicAdd(p.d_weights + k, WA[k]);
+    }
 }
 
 
@@ -391,6 +417,79 @@ __global__ void __launch_bounds__(256) nhwc_add_to_nchw_kernel(const float* __re
     for (int r = ty; r < 32; r += 8) {
         const int ch = c0 + r, pix = p0 + tx;
         if (ch < c && pix < hw) dst[((size_t)bi * c + ch) * hw + pix] += tile[tx][r];
+    }
+}
+
+// ---- the deterministic mode's reductions: no float atomics, a stated order of every sum --------------------------
+// out[k] += p[0][k] + p[1][k] + ... + p[g - 1][k]: the rows of a partials buffer [g][n] (one row per workgroup of a backward kernel) in
+// ascending workgroup order, plain fp32 adds, one thread per k.
+__global__ void __launch_bounds__(256) reduce_partials_kernel(const float* __restrict__ partials, int g, long long n, float* __restrict__ out) {
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
+        float s = partials[k];
+        for (int r = 1; r < g; ++r) s += partials[(size_t)r * n + k];
+        out[k] += s;
+    }
+}
+
+// sort keys and tap weights of interpolate_backward_kernel's scatter: entry (point i, tap a) -> key image * fh * fw + texel, or
+// b * fh * fw (sorts behind every texel, never read) where the original skips the tap (mask 0 or weight 0); wts [b * n][4]
+__global__ void interpolate_scatter_keys_kernel(const float* __restrict__ points, const float* __restrict__ mask, int b, int n, int fh, int fw,
+                                                int h_full, int w_full, int align, int* __restrict__ keys, float* __restrict__ wts) {
+    const long long total = (long long)b * n;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int bi = (int)(i / n);
+        const float mk = mask ? mask[i] : 1.0f;
+        const float ix = texel_coord(points[2 * i], (float)w_full, (float)fw, align != 0);
+        const float iy = texel_coord(points[2 * i + 1], (float)h_full, (float)fh, align != 0);
+        const Taps t = taps_from(ix, iy, fw, fh);
+        const int offs[4] = {t.o00, t.o10, t.o01, t.o11};
+        const float w4[4] = {t.w00, t.w10, t.w01, t.w11};
+        for (int a = 0; a < 4; ++a) {
+            keys[4 * i + a] = (mk != 0.0f && w4[a] != 0.0f) ? bi * fh * fw + offs[a] : b * fh * fw;
+            wts[4 * i + a] = w4[a];
+        }
+    }
+}
+
+// The scatter as a segmented sum.  keys: the entries' keys sorted ascending by a STABLE sort, perm: the entry (column * 4 + tap) at each
+// sorted position.  One wave per texel t: the run of keys == t is found by bisection and walked in sorted order - ascending (column, tap) -
+// with  acc = acc + w * (g [* mask])  per channel (lane = channel; no contraction), then one plain  out += acc  per channel.
+//   g [columns][g_stride] gradient rows, w of entry e at wts[(e >> 2) * w_stride + (e & 3)], mask [columns] or null (multiplied into g)
+//   channel ch of texel t = (image, pixel) = (t / hw, t % hw):  (ch < split ? out0 + ch * ch_stride : out1 + (ch - split) * ch_stride)
+//                                                                + image * img_stride + pixel * tex_stride
+struct ScatterSortedParams {
+    const int* keys; const long long* perm; const float* g; const float* wts; const float* mask;
+    float* out0; float* out1;
+    long long m, img_stride, tex_stride, ch_stride;
+    int ntex, hw, c, split, g_stride, w_stride;
+};
+__device__ __forceinline__ long long scatter_lower_bound(const int* __restrict__ keys, long long m, int t) {
+    long long lo = 0, hi = m;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (keys[mid] < t) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__global__ void __launch_bounds__(256) scatter_sorted_kernel(ScatterSortedParams p) {
+    const int lane = threadIdx.x & 63;
+    const int nwv = (int)(blockDim.x >> 6);
+    for (long long t = (long long)blockIdx.x * nwv + (threadIdx.x >> 6); t < p.ntex; t += (long long)gridDim.x * nwv) {
+        const long long lo = scatter_lower_bound(p.keys, p.m, (int)t), hi = scatter_lower_bound(p.keys, p.m, (int)t + 1);
+        if (lo == hi) continue;
+        const long long img = t / p.hw, pix = t - img * p.hw;
+        for (int ch = lane; ch < p.c; ch += 64) {
+            float acc = 0.0f;
+            for (long long i = lo; i < hi; ++i) {
+                const long long e = p.perm[i], col = e >> 2;
+                const float w = p.wts[col * p.w_stride + (e & 3)];
+                float gv = p.g[col * p.g_stride + ch];
+                if (p.mask) gv *= p.mask[col];
+                acc += w * gv;
+            }
+            float* dst = (ch < p.split ? p.out0 + ch * p.ch_stride : p.out1 + (ch - p.split) * p.ch_stride) + img * p.img_stride + pix * p.tex_stride;
+            *dst += acc;
+        }
     }
 }
 

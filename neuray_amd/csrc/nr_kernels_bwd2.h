@@ -175,7 +175,9 @@ __device__ __forceinline__ void dw_jobs(v4f (&acc)[dw_acc_n(NWV)], float (&bacc)
 }
 
 // end of the launch: this wave's accumulators of tensor ID -> global gradient buffer (natural layout)
-template <int ID, int NWV = kB2Waves>
+// DET (the deterministic mode): d_flat is the workgroup's own row of a zeroed partials buffer [gridDim.x][kFlatPassFloats]
+// and every word is written by one lane of one wave: plain stores; reduce_partials_kernel adds the rows in workgroup order.
+template <int ID, int NWV = kB2Waves, bool DET = false>
 __device__ __forceinline__ void dw_flush(const v4f (&acc)[dw_acc_n(NWV)], const float (&bacc)[dw_bias_n(NWV)], float* d_flat, int wave, int lane) {
     constexpr int OT = dw_ot(ID), KT = dw_kt(ID), J0 = dw_job0(ID), B0 = dw_bias0(ID);
     constexpr DwSpec sp = kDw[ID];
@@ -191,7 +193,8 @@ __device__ __forceinline__ void dw_flush(const v4f (&acc)[dw_acc_n(NWV)], const 
                 NR_PRAGMA_UNROLL
                 for (int r = 0; r < 4; ++r) {
                     const int o = 16 * a + 4 * kk + r, k = 16 * b + m;
-                    if (o < sp.O && k < sp.K) atomicAdd(d_flat + tensor_offset(sp.tw) + o * sp.ldw + sp.col0 + k, d[r] * xs);
+                    if constexpr (DET) { if (o < sp.O && k < sp.K) d_flat[tensor_offset(sp.tw) + o * sp.ldw + sp.col0 + k] = d[r] * xs; }
+                    else { if (o < sp.O && k < sp.K) atomicAdd(d_flat + tensor_offset(sp.tw) + o * sp.ldw + sp.col0 + k, d[r] * xs); }
                 }
             }
         }
@@ -200,7 +203,8 @@ __device__ __forceinline__ void dw_flush(const v4f (&acc)[dw_acc_n(NWV)], const 
             if (bj % NWV == wave) {
                 const float s = nr_group_sum(bacc[bj / NWV]);          // the four column subsets kk
                 const int o = 16 * a + m;
-                if (kk == 0 && o < sp.O) atomicAdd(d_flat + tensor_offset(sp.tb) + o, s);
+                if constexpr (DET) { if (kk == 0 && o < sp.O) d_flat[tensor_offset(sp.tb) + o] = s; }
+                else { if (kk == 0 && o < sp.O) atomicAdd(d_flat + tensor_offset(sp.tb) + o, s); }
             }
         }
     }
@@ -342,12 +346,19 @@ __device__ __forceinline__ void b2_dist_head_bwd(nr_wbuf W, nr_wbuf WT, int wlan
     B2_MARK(40);
 }
 
-template <int... IDS>
+template <bool DET, int... IDS>
 __device__ __forceinline__ void dw_flush_all(const v4f (&acc)[kDwAcc], const float (&bacc)[kDwBiasAcc], float* d_flat, int wave, int lane) {
-    (dw_flush<IDS>(acc, bacc, d_flat, wave, lane), ...);
+    (dw_flush<IDS, kB2Waves, DET>(acc, bacc, d_flat, wave, lane), ...);
 }
 
-template <bool HAS_VIS, int PART>
+// floats per (point, view) column of the deterministic mode's row buffer: d f_ray (32), d f_img (32), four tap offsets, four masked weights
+constexpr int kB2ScatterRow = 72;
+
+// DET: no float atomics.  p.d_flat is a zeroed partials buffer [gridDim.x][kFlatPassFloats]; the front half writes, instead
+// of scattering, the slab of every column - column index (point * 8 + view) - to p.d_ray_feats = rows [ceil(npts / 16) * 16 * 8][kB2ScatterRow]
+// and the sort keys (view * fh * fw + texel; rfn * fh * fw where the tap's masked weight is 0) to p.d_img_feats = int keys [columns][4];
+// scatter_sorted_kernel (nr_kernels_bwd.h) adds them per texel in ascending (column, tap) order.
+template <bool HAS_VIS, int PART, bool DET = false>
 __global__ void __launch_bounds__(512, 2) points_backward2_kernel(PointBwd2Params p) {
     constexpr bool DO_TAIL = PART == B2_TAIL, DO_FRONT = PART == B2_FRONT;
     NR_DYNAMIC_SMEM(float, smem);
@@ -952,6 +963,18 @@ __global__ void __launch_bounds__(512, 2) points_backward2_kernel(PointBwd2Param
                 slab[c * 72 + 68] = tfs.w00 * sc; slab[c * 72 + 69] = tfs.w10 * sc; slab[c * 72 + 70] = tfs.w01 * sc; slab[c * 72 + 71] = tfs.w11 * sc;
             }
             __syncthreads();
+            if constexpr (DET) {
+                float* rows = p.d_ray_feats + ((size_t)base * kB2Waves + wave) * kB2ScatterRow;
+                int* keys = reinterpret_cast<int*>(p.d_img_feats) + ((size_t)base * kB2Waves + wave) * 4;
+                for (int l = 0; l < 16; ++l) {
+                    float* row = rows + (size_t)l * kB2Waves * kB2ScatterRow;
+                    row[lane] = slab[l * 72 + lane];
+                    if (lane < 8) row[64 + lane] = slab[l * 72 + 64 + lane];
+                }
+                const int l = lane >> 2, tap = lane & 3, texels = p.fh * p.fw;
+                const bool on = slab[l * 72 + 68 + tap] != 0.0f;
+                keys[(size_t)l * kB2Waves * 4 + tap] = on ? view * texels + __float_as_int(slab[l * 72 + 64 + tap]) : p.rfn * texels;
+            } else {
             const int ch = lane & 31, half = lane >> 5;
             const size_t voff = (size_t)view * fmap;
             for (int l = 0; l < 16; ++l) {
@@ -967,6 +990,7 @@ __global__ void __launch_bounds__(512, 2) points_backward2_kernel(PointBwd2Param
                     }
                 }
             }
+            }
             __syncthreads();
             B2_MARK(42);
         }
@@ -974,11 +998,12 @@ __global__ void __launch_bounds__(512, 2) points_backward2_kernel(PointBwd2Param
         }
     }
     // ================= end of the launch: accumulated weight gradients -> global =================
+    float* const d_flat = DET ? p.d_flat + (size_t)blockIdx.x * kFlatPassFloats : p.d_flat;
     if constexpr (DO_TAIL)
-        dw_flush_all<DW_RF4, DW_RF2, DW_RF0, DW_V22, DW_V20, DW_VF2, DW_VF0, DW_B2, DW_BV, DW_GF2, DW_GF0, DW_BG>(acc, bacc, p.d_flat, wave, lane);
+        dw_flush_all<DET, DW_RF4, DW_RF2, DW_RF0, DW_V22, DW_V20, DW_VF2, DW_VF0, DW_B2, DW_BV, DW_GF2, DW_GF0, DW_BG>(acc, bacc, d_flat, wave, lane);
     if constexpr (DO_FRONT) {
-        dw_flush_all<DW_NF2, DW_NF0, DW_RD2, DW_RD0, DW_PE2, DW_PE0, DW_M4, DW_M2, DW_M0, DW_V4, DW_V2, DW_V0, DW_A4, DW_A2, DW_A0>(acc, bacc, p.d_flat, wave, lane);
-        if constexpr (HAS_VIS) dw_flush_all<DW_S4, DW_S2, DW_S0>(acc, bacc, p.d_flat, wave, lane);
+        dw_flush_all<DET, DW_NF2, DW_NF0, DW_RD2, DW_RD0, DW_PE2, DW_PE0, DW_M4, DW_M2, DW_M0, DW_V4, DW_V2, DW_V0, DW_A4, DW_A2, DW_A0>(acc, bacc, d_flat, wave, lane);
+        if constexpr (HAS_VIS) dw_flush_all<DET, DW_S4, DW_S2, DW_S0>(acc, bacc, d_flat, wave, lane);
     }
 }
 
@@ -1037,7 +1062,7 @@ __device__ __forceinline__ void sh_tiles(v4f (&acc)[kShAcc], float (&bacc)[kShBi
         bacc[B0 + a] += (av.x + av.y) + (av.z + av.w);
     }
 }
-template <int ID>
+template <int ID, bool DET = false>        // DET: d_flat = the workgroup's row of a zeroed partials buffer, plain stores (as dw_flush)
 __device__ __forceinline__ void sh_flush(const v4f (&acc)[kShAcc], const float (&bacc)[kShBias], float* d_flat, int lane) {
     constexpr int OT = dw_ot(ID), KT = dw_kt(ID), J0 = sh_job0(ID), B0 = sh_bias0(ID);
     constexpr DwSpec sp = kDw[ID];
@@ -1051,12 +1076,14 @@ __device__ __forceinline__ void sh_flush(const v4f (&acc)[kShAcc], const float (
             NR_PRAGMA_UNROLL
             for (int r = 0; r < 4; ++r) {
                 const int o = 16 * a + 4 * kk + r, k = 16 * b + m;
-                if (o < sp.O && k < sp.K) atomicAdd(d_flat + tensor_offset(sp.tw) + o * sp.ldw + sp.col0 + k, d[r] * xs);
+                if constexpr (DET) { if (o < sp.O && k < sp.K) d_flat[tensor_offset(sp.tw) + o * sp.ldw + sp.col0 + k] = d[r] * xs; }
+                else { if (o < sp.O && k < sp.K) atomicAdd(d_flat + tensor_offset(sp.tw) + o * sp.ldw + sp.col0 + k, d[r] * xs); }
             }
         }
         const float sb = nr_group_sum(bacc[B0 + a]);
         const int o = 16 * a + m;
-        if (kk == 0 && o < sp.O) atomicAdd(d_flat + tensor_offset(sp.tb) + o, sb);
+        if constexpr (DET) { if (kk == 0 && o < sp.O) d_flat[tensor_offset(sp.tb) + o] = sb; }
+        else { if (kk == 0 && o < sp.O) atomicAdd(d_flat + tensor_offset(sp.tb) + o, sb); }
     }
 }
 
@@ -1094,7 +1121,7 @@ __device__ __forceinline__ void sh_head_bwd(nr_wbuf W, nr_wbuf WT, int wlane, in
     sh_tiles<D0>(acc, bacc, S, 112, 144, lane);
 }
 
-template <bool HAS_VIS>
+template <bool HAS_VIS, bool DET = false>       // DET: p.d_flat is a zeroed partials buffer [gridDim.x][kFlatPassFloats]
 __global__ void __launch_bounds__(64) self_hit_backward2_kernel(SelfHitBwd2Params p) {
     __shared__ __attribute__((aligned(16))) float S[kShStageRows * kB2PStride];
     const int lane = threadIdx.x & 63;
@@ -1160,11 +1187,12 @@ __global__ void __launch_bounds__(64) self_hit_backward2_kernel(SelfHitBwd2Param
             *reinterpret_cast<float4*>(o + 4) = make_float4(dfr[4], dfr[5], dfr[6], dfr[7]);
         }
     }
-    sh_flush<DW_M4>(acc, bacc, p.d_flat, lane); sh_flush<DW_M2>(acc, bacc, p.d_flat, lane); sh_flush<DW_M0>(acc, bacc, p.d_flat, lane);
-    sh_flush<DW_V4>(acc, bacc, p.d_flat, lane); sh_flush<DW_V2>(acc, bacc, p.d_flat, lane); sh_flush<DW_V0>(acc, bacc, p.d_flat, lane);
-    sh_flush<DW_A4>(acc, bacc, p.d_flat, lane); sh_flush<DW_A2>(acc, bacc, p.d_flat, lane); sh_flush<DW_A0>(acc, bacc, p.d_flat, lane);
+    float* const d_flat = DET ? p.d_flat + (size_t)blockIdx.x * kFlatPassFloats : p.d_flat;
+    sh_flush<DW_M4, DET>(acc, bacc, d_flat, lane); sh_flush<DW_M2, DET>(acc, bacc, d_flat, lane); sh_flush<DW_M0, DET>(acc, bacc, d_flat, lane);
+    sh_flush<DW_V4, DET>(acc, bacc, d_flat, lane); sh_flush<DW_V2, DET>(acc, bacc, d_flat, lane); sh_flush<DW_V0, DET>(acc, bacc, d_flat, lane);
+    sh_flush<DW_A4, DET>(acc, bacc, d_flat, lane); sh_flush<DW_A2, DET>(acc, bacc, d_flat, lane); sh_flush<DW_A0, DET>(acc, bacc, d_flat, lane);
     if constexpr (HAS_VIS) {
-        sh_flush<DW_S4>(acc, bacc, p.d_flat, lane); sh_flush<DW_S2>(acc, bacc, p.d_flat, lane); sh_flush<DW_S0>(acc, bacc, p.d_flat, lane);
+        sh_flush<DW_S4, DET>(acc, bacc, d_flat, lane); sh_flush<DW_S2, DET>(acc, bacc, d_flat, lane); sh_flush<DW_S0, DET>(acc, bacc, d_flat, lane);
     }
 }
 
@@ -1188,7 +1216,7 @@ struct RowsBwd2Params {
     float var_bias;
 };
 
-template <bool HAS_VIS>
+template <bool HAS_VIS, bool DET = false>       // DET: p.d_flat is a zeroed partials buffer [gridDim.x][kFlatPassFloats]
 __global__ void __launch_bounds__(64) decoder_rows_backward2_kernel(RowsBwd2Params p) {
     __shared__ __attribute__((aligned(16))) float S[kShStageRows * kB2PStride];
     const int lane = threadIdx.x & 63;
@@ -1246,11 +1274,12 @@ __global__ void __launch_bounds__(64) decoder_rows_backward2_kernel(RowsBwd2Para
         }
     }
     // (only the heads that received a gradient: the flush is one atomicAdd per weight and workgroup)
-    if (p.d_mean) { sh_flush<DW_M4>(acc, bacc, p.d_flat, lane); sh_flush<DW_M2>(acc, bacc, p.d_flat, lane); sh_flush<DW_M0>(acc, bacc, p.d_flat, lane); }
-    if (p.d_var) { sh_flush<DW_V4>(acc, bacc, p.d_flat, lane); sh_flush<DW_V2>(acc, bacc, p.d_flat, lane); sh_flush<DW_V0>(acc, bacc, p.d_flat, lane); }
-    if (p.d_aw) { sh_flush<DW_A4>(acc, bacc, p.d_flat, lane); sh_flush<DW_A2>(acc, bacc, p.d_flat, lane); sh_flush<DW_A0>(acc, bacc, p.d_flat, lane); }
+    float* const d_flat = DET ? p.d_flat + (size_t)blockIdx.x * kFlatPassFloats : p.d_flat;
+    if (p.d_mean) { sh_flush<DW_M4, DET>(acc, bacc, d_flat, lane); sh_flush<DW_M2, DET>(acc, bacc, d_flat, lane); sh_flush<DW_M0, DET>(acc, bacc, d_flat, lane); }
+    if (p.d_var) { sh_flush<DW_V4, DET>(acc, bacc, d_flat, lane); sh_flush<DW_V2, DET>(acc, bacc, d_flat, lane); sh_flush<DW_V0, DET>(acc, bacc, d_flat, lane); }
+    if (p.d_aw) { sh_flush<DW_A4, DET>(acc, bacc, d_flat, lane); sh_flush<DW_A2, DET>(acc, bacc, d_flat, lane); sh_flush<DW_A0, DET>(acc, bacc, d_flat, lane); }
     if constexpr (HAS_VIS) {
-        if (p.d_vis) { sh_flush<DW_S4>(acc, bacc, p.d_flat, lane); sh_flush<DW_S2>(acc, bacc, p.d_flat, lane); sh_flush<DW_S0>(acc, bacc, p.d_flat, lane); }
+        if (p.d_vis) { sh_flush<DW_S4, DET>(acc, bacc, d_flat, lane); sh_flush<DW_S2, DET>(acc, bacc, d_flat, lane); sh_flush<DW_S0, DET>(acc, bacc, d_flat, lane); }
     }
 }
 

@@ -27,6 +27,9 @@ __device__ __forceinline__ int reflect_index(int i, int n) {            // refle
 }
 
 // raw [planes][2] (zeroed): sum (x - K), sum (x - K)^2 over the plane, K = x[plane][0].  grid = (chunks, planes)
+// DET (the deterministic mode): raw is [planes][chunks][2], every workgroup stores its own pair; inorm_finish_kernel adds a
+// plane's pairs in workgroup order (the sums inside a workgroup - butterfly, then the waves in order - are fixed already).
+template <bool DET = false>
 __global__ void __launch_bounds__(256) inorm_stats_kernel(const float* __restrict__ x, int hw, float* __restrict__ raw) {
     const int plane = blockIdx.y;
     const float* px = x + (size_t)plane * hw;
@@ -55,9 +58,24 @@ __global__ void __launch_bounds__(256) inorm_stats_kernel(const float* __restric
     if (threadIdx.x == 0) {
         float a = 0.0f, b = 0.0f;
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { a += sh[0][w]; b += sh[1][w]; }
-        atomicAdd(raw + 2 * plane, a);
-        atomicAdd(raw + 2 * plane + 1, b);
+        if constexpr (DET) {
+            raw[2 * ((size_t)plane * gridDim.x + blockIdx.x)] = a;
+            raw[2 * ((size_t)plane * gridDim.x + blockIdx.x) + 1] = b;
+        } else {
+            atomicAdd(raw + 2 * plane, a);
+            atomicAdd(raw + 2 * plane + 1, b);
+        }
     }
+}
+
+// raw [planes][2] = the planes' pairs of partials [planes][chunks][2] added in chunk order (one thread per plane and component)
+__global__ void inorm_finish_kernel(const float* __restrict__ partials, int planes, int chunks, float* __restrict__ raw) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * planes) return;
+    const float* pp = partials + (size_t)(i >> 1) * chunks * 2 + (i & 1);
+    float s = pp[0];
+    for (int k = 1; k < chunks; ++k) s += pp[2 * k];
+    raw[i] = s;
 }
 
 struct NormApplyParams {
@@ -152,7 +170,8 @@ __device__ __forceinline__ float norm_bwd_g(const NormBwdParams& p, const float*
     return g * norm_act_grad(o_plane[(y + p.pad) * wp + xx + p.pad], p.act);
 }
 
-// grid = (chunks, planes)
+// grid = (chunks, planes).  DET: p.raw is [planes][chunks][2] (as inorm_stats_kernel<true>)
+template <bool DET = false>
 __global__ void __launch_bounds__(256) inorm_backward_reduce_kernel(NormBwdParams p) {
     const int plane = blockIdx.y, hw = p.h * p.w, hpwp = (p.h + 2 * p.pad) * (p.w + 2 * p.pad);
     const int img = plane / p.c, ch = plane - img * p.c;
@@ -177,8 +196,13 @@ __global__ void __launch_bounds__(256) inorm_backward_reduce_kernel(NormBwdParam
     if (threadIdx.x == 0) {
         float a = 0.0f, b = 0.0f;
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { a += sh[0][w]; b += sh[1][w]; }
-        atomicAdd(p.raw + 2 * plane, a);
-        atomicAdd(p.raw + 2 * plane + 1, b);
+        if constexpr (DET) {
+            p.raw[2 * ((size_t)plane * gridDim.x + blockIdx.x)] = a;
+            p.raw[2 * ((size_t)plane * gridDim.x + blockIdx.x) + 1] = b;
+        } else {
+            atomicAdd(p.raw + 2 * plane, a);
+            atomicAdd(p.raw + 2 * plane + 1, b);
+        }
     }
 }
 

@@ -121,6 +121,12 @@ class RenderEngine:
         self.timing = None
         self.max_backward_samples = _lib.MAX_BACKWARD_SAMPLES
         self.slot_stats = None                     # optional int64 device tensor [2]: every point-kernel launch adds (view slots run, view slots)
+        # the deterministic mode: a running total of the scratch bytes its calls have allocated (partials, row buffers, sort
+        # keys; every buffer is freed when its call's results are; the difference over one step is the step's extra memory; stays 0 while
+        # the mode is off)
+        self.det_scratch_bytes = 0
+        self.keep_norm_partials = False            # tests: keep the last deterministic fused-norm call's (partials, sums) in norm_partials
+        self.norm_partials = {}
 
     # ------------------------------------------------------------------------------------------
     def _stream(self):
@@ -656,8 +662,31 @@ class RenderEngine:
         st[1].record(torch.cuda.current_stream(self.device))
         return dev
 
+    # ---- scratch of the deterministic mode -------------------------------------------------------------------
+    def _det_scratch(self, n, dtype=torch.float32, zero=False):
+        t = self.zeroed((int(n),))[0] if zero and dtype == torch.float32 else self.empty(int(n), dtype=dtype)
+        self.det_scratch_bytes += t.numel() * t.element_size()
+        return t
+
+    def _det_partials(self, kernel, rn, dn=0):
+        """the zeroed partials buffer [workgroups][floats] of one backward kernel (_lib.DET_*)"""
+        return self._det_scratch(self.lib.neuray_deterministic_partials_floats(kernel, int(rn), int(dn)), zero=True)
+
+    def _det_sort(self, keys):
+        """-> (keys sorted ascending by a STABLE sort, int64 permutation): the order of every texel's sum is ascending entry index"""
+        skeys, perm = torch.sort(keys, stable=True)
+        self.det_scratch_bytes += skeys.numel() * skeys.element_size() + perm.numel() * perm.element_size()
+        return skeys, perm
+
+    def reduce_partials(self, partials, out):
+        """out [n] += partials[0] + partials[1] + ... in row order, plain fp32 adds (neuray_reduce_partials)"""
+        g, n = partials.shape
+        assert partials.is_contiguous() and out.is_contiguous() and out.numel() == n
+        self._check(self.lib.neuray_reduce_partials(partials.data_ptr(), g, n, out.data_ptr(), self._stream()))
+        return out
+
     def render_points_backward(self, qconst, views, coords, depth, flat, has_vis_head, use_vis, d_point_rec, var_bias=0.05,
-                               packed=None, saved=None, out=None):
+                               packed=None, saved=None, out=None, deterministic=False):
         """Backward of the point kernel: -> (d_flat [flat pass floats], d_ray_feats NHWC [rfn,fh,fw,32], d_img_feats NHWC).
         The register / LDS resident kernel of csrc/nr_kernels_bwd2.h, run as its two halves (tail, front) with a hand-over buffer in
         between; at most 8 reference views (no shipped configuration trains with more: dataset/train_dataset.py:73-74,
@@ -684,11 +713,24 @@ class RenderEngine:
             views.fh, views.fw, int(has_vis_head), int(bool(use_vis)), float(var_bias),
             packed.dev.data_ptr(), pt.data_ptr(), saved.data_ptr(), ho.data_ptr())
         ev = self._event_pair()
-        self._check(self.lib.neuray_render_points_backward(C.byref(a), self._stream()))
+        if deterministic:
+            # no float atomics: per-workgroup partials of the weight gradients added in workgroup order; the maps' gradients as a
+            # segmented sum over stably sorted (texel, column, tap) keys
+            cols = int(self.lib.neuray_points_backward_scatter_columns(rn * dn))
+            part = self._det_partials(_lib.DET_POINTS, rn, dn)
+            rows = self._det_scratch(cols * 72)
+            keys = self._det_scratch(cols * 4, dtype=torch.int32)
+            self._check(self.lib.neuray_render_points_backward_det(C.byref(a), part.data_ptr(), rows.data_ptr(), keys.data_ptr(), self._stream()))
+            skeys, perm = self._det_sort(keys)
+            self._check(self.lib.neuray_points_backward_scatter(skeys.data_ptr(), perm.data_ptr(), rows.data_ptr(), cols, views.rfn, views.fh,
+                                                                views.fw, d_rf.data_ptr(), d_if.data_ptr(), self._stream()))
+        else:
+            self._check(self.lib.neuray_render_points_backward(C.byref(a), self._stream()))
         self._event_done(ev, 'points_backward', rn * dn)
         return d_flat, d_rf, d_if
 
-    def self_hit_prob_backward(self, qconst, depth, feats, flat, has_vis_head, use_vis, d_hit, var_bias=0.05, packed=None, d_flat=None):
+    def self_hit_prob_backward(self, qconst, depth, feats, flat, has_vis_head, use_vis, d_hit, var_bias=0.05, packed=None, d_flat=None,
+                               deterministic=False):
         """Backward of dist_decoder_rows + self_hit_prob: -> (d_feats [rn,32], d_flat).  One wave per 16 rays, the decoder in registers on
         the packed / transposed packs.  d_flat: an existing flat gradient buffer to accumulate into (the kernel adds atomically) instead
         of a fresh zeroed one."""
@@ -700,12 +742,17 @@ class RenderEngine:
             raise ValueError("neuray_amd: the backward kernels take the unfolded pack (pack_pass(fold=False) / pack_pass_device)")
         pk = (packed if packed is not None else self.pack_pass_device(flat, bool(has_vis_head))).dev
         pt = self.pack_pass_t_device(flat, bool(has_vis_head))
-        self._check(self.lib.neuray_self_hit_prob_backward(
-            qconst.data_ptr(), depth.data_ptr(), feats.data_ptr(), pk.data_ptr(), pt.data_ptr(), int(has_vis_head), int(bool(use_vis)),
-            float(var_bias), d_hit.data_ptr(), rn, dn, d_feats.data_ptr(), d_flat.data_ptr(), self._stream()))
+        args = (qconst.data_ptr(), depth.data_ptr(), feats.data_ptr(), pk.data_ptr(), pt.data_ptr(), int(has_vis_head), int(bool(use_vis)),
+                float(var_bias), d_hit.data_ptr(), rn, dn, d_feats.data_ptr(), d_flat.data_ptr())
+        if deterministic:
+            part = self._det_partials(_lib.DET_SELF_HIT, rn, dn)
+            self._check(self.lib.neuray_self_hit_prob_backward_det(*args, part.data_ptr(), self._stream()))
+        else:
+            self._check(self.lib.neuray_self_hit_prob_backward(*args, self._stream()))
         return d_feats, d_flat
 
-    def dist_decoder_rows_backward(self, feats, flat, has_vis_head, var_bias, d_mean=None, d_var=None, d_aw=None, d_vis=None, packed=None):
+    def dist_decoder_rows_backward(self, feats, flat, has_vis_head, var_bias, d_mean=None, d_var=None, d_aw=None, d_vis=None, packed=None,
+                                   deterministic=False):
         """Backward of dist_decoder_rows: -> (d_feats [n,32], d_flat).  One wave per 16 rows, the heads in registers on the packed /
         transposed packs; heads without an incoming gradient are skipped."""
         feats = self._f32(feats).reshape(-1, 32)
@@ -716,13 +763,20 @@ class RenderEngine:
         ptr = lambda t: t.data_ptr() if t is not None else None       # noqa: E731
         pk = (packed if packed is not None else self.pack_pass_device(flat, bool(has_vis_head))).dev
         pt = self.pack_pass_t_device(flat, bool(has_vis_head))
-        self._check(self.lib.neuray_dist_decoder_rows_backward(
-            feats.data_ptr(), pk.data_ptr(), pt.data_ptr(), n, int(has_vis_head), float(var_bias), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]),
-            d_feats.data_ptr(), d_flat.data_ptr(), self._stream()))
+        args = (feats.data_ptr(), pk.data_ptr(), pt.data_ptr(), n, int(has_vis_head), float(var_bias), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]),
+                d_feats.data_ptr(), d_flat.data_ptr())
+        if deterministic:
+            part = self._det_partials(_lib.DET_ROWS, n)
+            self._check(self.lib.neuray_dist_decoder_rows_backward_det(*args, part.data_ptr(), self._stream()))
+        else:
+            self._check(self.lib.neuray_dist_decoder_rows_backward(*args, self._stream()))
         return d_feats, d_flat
 
-    def interpolate_feats_backward(self, d_out, feats_shape, points, h=None, w=None, align_corners=False, mask=None, out=None, staged=None):
-        """Backward of interpolate_feats w.r.t. the feature maps: -> d_feats [b,c,fh,fw] (out: a zeroed buffer to add into)"""
+    def interpolate_feats_backward(self, d_out, feats_shape, points, h=None, w=None, align_corners=False, mask=None, out=None, staged=None,
+                                   deterministic=False):
+        """Backward of interpolate_feats w.r.t. the feature maps: -> d_feats [b,c,fh,fw] (out: a zeroed buffer to add into).
+        deterministic: no atomics - every texel's sum runs in ascending (point, tap 00, 10, 01, 11) order, acc += w * (d_out * mask) in fp32,
+        then one d_feats += acc"""
         d_out, points = self._f32(d_out), self._f32(points)
         b, c, fh, fw = feats_shape
         n = points.shape[1]
@@ -730,6 +784,17 @@ class RenderEngine:
             h, w = fh, fw
         d_feats = out if out is not None else torch.zeros(b, c, fh, fw, dtype=torch.float32, device=self.device)
         m = self._f32(mask) if mask is not None else None
+        if deterministic:
+            keys = self._det_scratch(b * n * 4, dtype=torch.int32)
+            wts = self._det_scratch(b * n * 4)
+            self._check(self.lib.neuray_interpolate_scatter_keys(points.data_ptr(), m.data_ptr() if m is not None else None, b, n, fh, fw,
+                                                                 int(h), int(w), int(bool(align_corners)), keys.data_ptr(), wts.data_ptr(),
+                                                                 self._stream()))
+            skeys, perm = self._det_sort(keys)
+            self._check(self.lib.neuray_interpolate_feats_backward_sorted(
+                d_out.data_ptr(), m.data_ptr() if m is not None else None, skeys.data_ptr(), perm.data_ptr(), wts.data_ptr(), b, n, c, fh, fw,
+                d_feats.data_ptr(), self._stream()))
+            return d_feats
         if staged is None:            # many points per map: scatter into a channels-last staging map (coalesced atomics), then transpose-add
             # ... when the points are dense enough to pay for the zero-filled staging map and its transpose-add (1 024 points on
             # 8 x 32 x 800 x 800 maps would allocate and sweep 655 MB for a 128 KB scatter), and the map stays below 256 MB
@@ -745,7 +810,8 @@ class RenderEngine:
                                                                d_feats.data_ptr(), self._stream()))
         return d_feats
 
-    def render_rays_backward(self, point_rec, depth, packed, d_pixel, d_hit_prob=None, d_render_depth=None, att_saved=None, d_w=None):
+    def render_rays_backward(self, point_rec, depth, packed, d_pixel, d_hit_prob=None, d_render_depth=None, att_saved=None, d_w=None,
+                             deterministic=False):
         """Backward of the ray kernel (attention, sigma head, compositing): gradients of a scalar loss w.r.t. the
         per-point records [rn,dn,POINT_REC] (geometry feature 0..15, colour 16..18) and the ray-part weights.
         att_saved: render_pass(save=True)['att_saved'] (the forward's softmax statistics; recomputed if absent).
@@ -762,7 +828,11 @@ class RenderEngine:
             point_rec.data_ptr(), depth.data_ptr(), self.posenc(dn).data_ptr(), packed.dev.data_ptr(), d_pixel.data_ptr(),
             dh.data_ptr() if dh is not None else None, dd.data_ptr() if dd is not None else None,
             d_rec.data_ptr(), d_w.data_ptr(), rn, dn, att_saved.data_ptr() if att_saved is not None else None)
-        self._check(self.lib.neuray_render_rays_backward(C.byref(a), self._stream()))
+        if deterministic:
+            part = self._det_scratch(self.lib.neuray_deterministic_partials_floats(_lib.DET_RAYS, rn, dn))       # (every word is written)
+            self._check(self.lib.neuray_render_rays_backward_det(C.byref(a), part.data_ptr(), self._stream()))
+        else:
+            self._check(self.lib.neuray_render_rays_backward(C.byref(a), self._stream()))
         grads = {name: d_w[off:off + int(np.prod(shape))].view(*shape) for name, off, shape in _lib.RAY_WEIGHT_SLOTS}
         return d_rec, grads
 
@@ -928,7 +998,7 @@ class RenderEngine:
         return d_dec
 
     def direct_render_backward(self, qconst, views, coords, depth, view_rec, regs, alpha, colors, d_pixel, d_hit_prob, ray_feats, flat,
-                               has_vis_head, use_vis, var_bias=0.05, packed=None):
+                               has_vis_head, use_vis, var_bias=0.05, packed=None, deterministic=False):
         """Backward of direct_render (SH colours) down to the pass's dist decoder and its input map: the two dr backward kernels, then
         the decoder rows at the recorded (u, v) - interpolate_feats of ray_feats (NCHW [rfn,32,fh,fw], renderer.py:67-72 /
         render_ops.py:54-70) - through dist_decoder_rows_backward, and interpolate_feats_backward with the mask.
@@ -945,9 +1015,9 @@ class RenderEngine:
         g = d_dec.view(rn * dn, rfn, 6).transpose(0, 1)
         d_feats, d_flat = self.dist_decoder_rows_backward(
             feats, flat, has_vis_head, var_bias, d_mean=g[..., 0:2].contiguous(), d_var=g[..., 2:4].contiguous(),
-            d_aw=g[..., 4].contiguous(), d_vis=g[..., 5].contiguous() if has_vis_head else None, packed=packed)
+            d_aw=g[..., 4].contiguous(), d_vis=g[..., 5].contiguous() if has_vis_head else None, packed=packed, deterministic=deterministic)
         d_map = self.interpolate_feats_backward(d_feats.view(rfn, rn * dn, 32), tuple(ray_feats.shape), pts, views.h, views.w,
-                                                align_corners=False, mask=mask)
+                                                align_corners=False, mask=mask, deterministic=deterministic)
         return d_map, d_flat
 
     def render_rays(self, point_rec, depth, packed, save=False, ray_mask_view_num=2, ray_mask_point_num=8):

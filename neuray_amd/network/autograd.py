@@ -11,7 +11,9 @@ from .. import _lib
 class PassRun:
     """Everything one render pass needs besides the differentiable tensors."""
 
-    def __init__(self, eng, qconst, views, coords, depth, dist, agg, use_vis, var_bias, mask_view_num, mask_point_num, want_depth):
+    def __init__(self, eng, qconst, views, coords, depth, dist, agg, use_vis, var_bias, mask_view_num, mask_point_num, want_depth,
+                 deterministic=False):
+        self.deterministic = bool(deterministic)       # the backward kernels without float atomics (cfg['hip_deterministic'], DESIGN.md 4.18)
         self.eng, self.qconst, self.views, self.coords, self.depth = eng, qconst, views, coords, depth
         self.dist, self.agg, self.use_vis, self.var_bias = dist, agg, use_vis, var_bias
         self.mask_view_num, self.mask_point_num, self.want_depth = mask_view_num, mask_point_num, want_depth
@@ -80,11 +82,12 @@ class RenderPassFn(torch.autograd.Function):
         d_flat, d_w, d_rf, d_if = eng.zeroed(ctx.flat.shape, (_lib.PACKED_RAY_FLOATS,), run.views.ray_feats.shape, run.views.img_feats.shape)
         d_rec, g_ray = eng.render_rays_backward(point_rec, run.depth, ctx.packed, d_pixel.contiguous(),
                                                 d_hit.contiguous() if d_hit is not None else None,
-                                                d_depth.contiguous() if d_depth is not None else None, att_saved=ctx.att_saved, d_w=d_w)
+                                                d_depth.contiguous() if d_depth is not None else None, att_saved=ctx.att_saved, d_w=d_w,
+                                                deterministic=run.deterministic)
         sd = run.state()
         d_flat, d_rf, d_if = eng.render_points_backward(run.qconst, run.views, run.coords, run.depth, ctx.flat, ctx.has_vis,
                                                         run.use_vis, d_rec, var_bias=run.var_bias, packed=ctx.packed,
-                                                        saved=ctx.point_saved, out=(d_flat, d_rf, d_if))
+                                                        saved=ctx.point_saved, out=(d_flat, d_rf, d_if), deterministic=run.deterministic)
         grads = eng.unflatten_pass_grads(d_flat, sd, 'd.', 'a.')
         for name, g in g_ray.items():
             grads['a.agg_impl.' + name] = g
@@ -131,16 +134,18 @@ class RenderPassSelfFn(torch.autograd.Function):
                                                     run.views.img_feats.shape, ctx.que_shape if want_map else (1,))
         d_rec, g_ray = eng.render_rays_backward(point_rec, run.depth, ctx.packed, d_pixel.contiguous(),
                                                 d_hit.contiguous() if d_hit is not None else None,
-                                                d_depth.contiguous() if d_depth is not None else None, att_saved=ctx.att_saved, d_w=d_w)
+                                                d_depth.contiguous() if d_depth is not None else None, att_saved=ctx.att_saved, d_w=d_w,
+                                                deterministic=run.deterministic)
         d_flat, d_rf, d_if = eng.render_points_backward(run.qconst, run.views, run.coords, run.depth, ctx.flat, ctx.has_vis,
                                                         run.use_vis, d_rec, var_bias=run.var_bias, packed=ctx.packed,
-                                                        saved=ctx.point_saved, out=(d_flat, d_rf, d_if))
+                                                        saved=ctx.point_saved, out=(d_flat, d_rf, d_if), deterministic=run.deterministic)
         if d_hit_self is not None:
             d_feats, _ = eng.self_hit_prob_backward(run.qconst, run.depth, feats[0], ctx.flat, ctx.has_vis, ctx.self_use_vis,
-                                                    d_hit_self.contiguous(), var_bias=run.var_bias, packed=ctx.packed, d_flat=d_flat)
+                                                    d_hit_self.contiguous(), var_bias=run.var_bias, packed=ctx.packed, d_flat=d_flat,
+                                                    deterministic=run.deterministic)
             if want_map:
                 eng.interpolate_feats_backward(d_feats[None], ctx.que_shape, run.coords[None], ctx.hw[0], ctx.hw[1], align_corners=False,
-                                               out=d_map)
+                                               out=d_map, deterministic=run.deterministic)
         if not want_map:
             d_map = None
         grads = eng.unflatten_pass_grads(d_flat, run.state(), 'd.', 'a.')
@@ -172,8 +177,10 @@ class SelfHitFn(torch.autograd.Function):
         feats, = ctx.saved_tensors
         sd = run.state()
         d_feats, d_flat = eng.self_hit_prob_backward(run.qconst, run.depth, feats[0], ctx.flat, ctx.has_vis, run.use_vis,
-                                                     d_hit.contiguous(), var_bias=run.var_bias, packed=ctx.packed)
-        d_map = eng.interpolate_feats_backward(d_feats[None], ctx.shape, run.coords[None], ctx.hw[0], ctx.hw[1], align_corners=False)
+                                                     d_hit.contiguous(), var_bias=run.var_bias, packed=ctx.packed,
+                                                     deterministic=run.deterministic)
+        d_map = eng.interpolate_feats_backward(d_feats[None], ctx.shape, run.coords[None], ctx.hw[0], ctx.hw[1], align_corners=False,
+                                               deterministic=run.deterministic)
         grads = eng.unflatten_pass_grads(d_flat, sd, 'd.', 'a.')
         return (None, None, None, d_map) + tuple(grads[k] for k, _ in run.dist_params())
 
@@ -208,7 +215,7 @@ class DirectRenderFn(torch.autograd.Function):
         d_map, d_flat = eng.direct_render_backward(run.qconst, run.views, run.coords, run.depth, rec, ctx.regs, alpha, colors,
                                                    d_pixel.contiguous(), d_hit.contiguous() if d_hit is not None else None,
                                                    ray_feats.detach(), ctx.flat, ctx.has_vis, run.use_vis, var_bias=run.var_bias,
-                                                   packed=ctx.packed)
+                                                   packed=ctx.packed, deterministic=run.deterministic)
         grads = eng.unflatten_pass_grads(d_flat, run.state(), 'd.', 'a.')
         return (None, None, None, d_map if ctx.needs_input_grad[3] else None) + tuple(grads[k] for k, _ in run.dist_params())
 

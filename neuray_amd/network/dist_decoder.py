@@ -32,7 +32,9 @@ class _RowsFn(torch.autograd.Function):
         flat, has_vis = eng.flat_pass_device(named, 'd.', 'a.', allow_missing_agg=True)
         packed = eng.pack_pass_device(flat, has_vis)
         mean, var, vis, aw = eng.dist_decoder_rows(feats, packed, dec.cfg['bias_val'])
+        from . import fused_norm
         ctx.dec, ctx.flat, ctx.has_vis, ctx.packed = dec, flat, has_vis, packed
+        ctx.det = fused_norm.deterministic()      # the process-wide deterministic switch as it stands at the forward
         ctx.set_materialize_grads(False)          # an output the loss does not use arrives as None: its head's backward is skipped
         ctx.save_for_backward(feats.detach())
         if vis is None:
@@ -45,7 +47,7 @@ class _RowsFn(torch.autograd.Function):
         feats, = ctx.saved_tensors
         eng = dec._engine(feats.device)
         d_feats, d_flat = eng.dist_decoder_rows_backward(feats, ctx.flat, ctx.has_vis, dec.cfg['bias_val'], d_mean, d_var, d_aw,
-                                                         d_vis if ctx.has_vis else None, packed=ctx.packed)
+                                                         d_vis if ctx.has_vis else None, packed=ctx.packed, deterministic=ctx.det)
         sd = {'d.' + k: v.detach() for k, v in dec.named_parameters()}
         grads = eng.unflatten_pass_grads(d_flat, sd, 'd.', 'a.')
         # (views of the freshly allocated d_flat, as RenderPassFn returns them: no per-parameter copy)

@@ -8,6 +8,7 @@ reflection_pad2d), with a two-pass backward.  The result is handed to the next c
 (`conv_prepadded`); the un-padded activation is the interior view of the same buffer (`interior`).  On a device without the
 kernels (plain CPU) the same function composes the PyTorch ops, so the modules have one forward."""
 
+import os
 import weakref
 
 import numpy as np
@@ -16,6 +17,34 @@ import torch.nn.functional as F
 
 ACTS = {None: 0, 'relu': 1, 'elu': 2}
 FUSED_NORM = True          # False: always compose the PyTorch ops (A/B timing, tests)
+# The deterministic mode outside the render passes - the fused norm here (the InstanceNorm statistics, forward and backward,
+# as per-workgroup partials added in workgroup order instead of float atomics) and the stand-alone autograd functions of render_ops.py /
+# dist_decoder.py (the depth-loss path) - has no renderer cfg at hand and reads this process-wide switch through deterministic():
+#   DETERMINISTIC            False / True / 'auto' (= torch.are_deterministic_algorithms_enabled()): set it here directly;
+#   RENDERER_DETERMINISTIC   the cfg['hip_deterministic'] of the renderer that was constructed or ran render_impl last (written by
+#                            HipRenderPath._deterministic_mode, never by a user; it does not touch DETERMINISTIC);
+# the mode is on if either asks for it; the environment variable NEURAY_HIP_DETERMINISTIC = 0 / 1 wins over both.
+DETERMINISTIC = False
+RENDERER_DETERMINISTIC = False
+
+
+def resolve_deterministic(value):
+    """cfg['hip_deterministic'] / DETERMINISTIC -> bool; NEURAY_HIP_DETERMINISTIC wins (as NEURAY_HIP_ARITH over cfg['hip_arith'])"""
+    env = os.environ.get('NEURAY_HIP_DETERMINISTIC')
+    if env:
+        if env not in ('0', '1'):
+            raise ValueError("neuray_amd: NEURAY_HIP_DETERMINISTIC=%r (use 0 or 1)" % (env,))
+        return env == '1'
+    if isinstance(value, str) and value == 'auto':
+        return bool(torch.are_deterministic_algorithms_enabled())
+    if value is True or value is False:
+        return value
+    raise ValueError("neuray_amd: cfg['hip_deterministic'] = %r (use False, True or 'auto')" % (value,))
+
+
+def deterministic():
+    """the process-wide switch: the environment, else DETERMINISTIC or the last renderer's cfg"""
+    return resolve_deterministic(DETERMINISTIC) or resolve_deterministic(RENDERER_DETERMINISTIC)
 
 
 def _engine(device):
@@ -40,7 +69,8 @@ class _NormActFn(torch.autograd.Function):
         if ct:
             out[:, c:].copy_(tail)
         stats = torch.empty(n * c, 2, dtype=torch.float32, device=x.device)
-        raw = eng.zero_scratch(2 * n * c)
+        det = deterministic()
+        raw = eng.zero_scratch(2 * n * c) if not det else eng._det_scratch(2 * n * c)
         g, b = gamma.detach().contiguous().float(), beta.detach().contiguous().float()
         rs = (0, 0, 0)
         if res is not None:
@@ -48,31 +78,46 @@ class _NormActFn(torch.autograd.Function):
                 res = res.contiguous().float()
             assert tuple(res.shape) == (n, c, h, w), (tuple(res.shape), (n, c, h, w))
             rs = res.stride()[:3]
-        eng._check(eng.lib.neuray_inorm_forward(
-            x.data_ptr(), g.data_ptr(), b.data_ptr(), res.data_ptr() if res is not None else None, rs[0], rs[1], rs[2],
-            n, c, h, w, int(pad), int(act), float(eps), raw.data_ptr(), stats.data_ptr(), out.data_ptr(), (c + ct) * hp * wp, eng._stream()))
+        args = (x.data_ptr(), g.data_ptr(), b.data_ptr(), res.data_ptr() if res is not None else None, rs[0], rs[1], rs[2],
+                n, c, h, w, int(pad), int(act), float(eps))
+        if det:       # every workgroup's pair of sums -> partials; raw = their sum in workgroup order
+            chunks = int(eng.lib.neuray_inorm_chunks(n, c, h, w))
+            part = eng._det_scratch(n * c * chunks * 2)
+            eng._check(eng.lib.neuray_inorm_forward_det(*args, part.data_ptr(), raw.data_ptr(), stats.data_ptr(), out.data_ptr(),
+                                                        (c + ct) * hp * wp, eng._stream()))
+            if eng.keep_norm_partials:
+                eng.norm_partials['forward'] = (part.view(n * c, chunks, 2), raw[:2 * n * c].view(n * c, 2))
+        else:
+            eng._check(eng.lib.neuray_inorm_forward(*args, raw.data_ptr(), stats.data_ptr(), out.data_ptr(), (c + ct) * hp * wp, eng._stream()))
         ctx.save_for_backward(x, out, stats, g)
-        ctx.meta = (int(pad), int(act), res is not None, ct)
+        ctx.meta = (int(pad), int(act), res is not None, ct, det)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         x, out, stats, g = ctx.saved_tensors
-        pad, act, has_res, ct = ctx.meta
+        pad, act, has_res, ct, det = ctx.meta
         eng = _engine(x.device)
         n, c, h, w = x.shape
         d_out = d_out.contiguous().float()
         img = (c + ct) * (h + 2 * pad) * (w + 2 * pad)
-        raw = eng.zero_scratch(2 * n * c)[:2 * n * c]
+        raw = eng.zero_scratch(2 * n * c)[:2 * n * c] if not det else eng._det_scratch(2 * n * c)
         d_affine = torch.empty(2, c, dtype=torch.float32, device=x.device)
         d_gamma, d_beta = d_affine[0], d_affine[1]
         dx = torch.empty_like(x)
         d_res = torch.empty_like(x) if has_res else None
         # (the affine parameters' gradients come out of the apply kernel - the planes' sums added over the images - instead of one more
         # PyTorch reduction per call: 30 launches of ~15 us per encoder pass)
-        eng._check(eng.lib.neuray_inorm_backward(
-            x.data_ptr(), out.data_ptr(), img, d_out.data_ptr(), img, stats.data_ptr(), g.data_ptr(), n, c, h, w, pad, act, raw.data_ptr(),
-            dx.data_ptr(), d_res.data_ptr() if has_res else None, d_gamma.data_ptr(), d_beta.data_ptr(), eng._stream()))
+        args = (x.data_ptr(), out.data_ptr(), img, d_out.data_ptr(), img, stats.data_ptr(), g.data_ptr(), n, c, h, w, pad, act)
+        outs = (dx.data_ptr(), d_res.data_ptr() if has_res else None, d_gamma.data_ptr(), d_beta.data_ptr(), eng._stream())
+        if det:
+            chunks = int(eng.lib.neuray_inorm_chunks(n, c, h, w))
+            part = eng._det_scratch(n * c * chunks * 2)
+            eng._check(eng.lib.neuray_inorm_backward_det(*args, part.data_ptr(), raw.data_ptr(), *outs))
+            if eng.keep_norm_partials:
+                eng.norm_partials['backward'] = (part.view(n * c, chunks, 2), raw.view(n * c, 2))
+        else:
+            eng._check(eng.lib.neuray_inorm_backward(*args, raw.data_ptr(), *outs))
         return dx, d_gamma, d_beta, d_res, None, None, None, (d_out[:, c:] if ct else None)
 
 

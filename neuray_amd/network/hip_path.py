@@ -8,7 +8,8 @@ by the mirror classes of network/renderer.py.
 Replaced reference methods (same signatures): `render_by_depth` (renderer.py:168-203), `fine_render_impl` (:205-215),
 `render_impl` (:217-226), `predict_self_hit_prob` (:147-155).  cfg['hip_coarse_pass'] = 'visibility' (not a reference key; the
 environment variable NEURAY_HIP_COARSE wins) replaces the coarse network pass by the visibility estimate of the input views
-(`_visibility_coarse`): inference only, the fine pass is the only one that renders colours.  Under autograd each pass is a torch.autograd.Function
+(`_visibility_coarse`): inference only, the fine pass is the only one that renders colours.  cfg['hip_deterministic'] (False / True / 'auto'; NEURAY_HIP_DETERMINISTIC
+wins) runs the training backward without float atomics: bitwise reproducible gradients (`_deterministic_mode`).  Under autograd each pass is a torch.autograd.Function
 whose backward runs the backward kernels (network/autograd.py).  Anything the HIP path does not implement raises - it
 never silently switches to an eager implementation.
 """
@@ -17,10 +18,11 @@ import os
 import torch
 
 from ..engine import RenderEngine
+from . import fused_norm
 from .autograd import DirectRenderFn, PassRun, RenderPassFn, RenderPassSelfFn, SelfHitFn
 
 HOT_PATH_METHODS = ('engine', '_packed_pass', '_same_tensors', '_views', '_query', '_self_hit_prob', '_direct_rendering',
-                    '_coarse_pass_mode', '_visibility_coarse', 'render_by_depth', 'predict_self_hit_prob', 'fine_render_impl', 'render_impl')
+                    '_coarse_pass_mode', '_deterministic_mode', '_visibility_coarse', 'render_by_depth', 'predict_self_hit_prob', 'fine_render_impl', 'render_impl')
 
 
 class HipRenderPath:
@@ -85,7 +87,8 @@ class HipRenderPath:
         use_vis = self.dist_decoder.cfg['use_vis']                              # renderer.py:75: always the coarse decoder
         cfg = self.cfg
         run = PassRun(eng, qconst, views, coords[0].contiguous(), que_depth[0].detach().contiguous(), dist, agg, use_vis,
-                      dist.cfg['bias_val'], cfg['ray_mask_view_num'], cfg['ray_mask_point_num'], cfg['render_depth'])
+                      dist.cfg['bias_val'], cfg['ray_mask_view_num'], cfg['ray_mask_point_num'], cfg['render_depth'],
+                      deterministic=self._deterministic_mode())
         diff = [p for _, p in run.named_params()] + [ref_imgs_info['ray_feats'], ref_imgs_info['img_feats']]
         if torch.is_grad_enabled() and any(t.requires_grad for t in diff):
             if eng.variant not in ('fp32', 'bf16x3'):
@@ -183,7 +186,7 @@ class HipRenderPath:
         agg = self.fine_agg_net if is_fine else self.agg_net
         if torch.is_grad_enabled() and (que_imgs_info['ray_feats'].requires_grad or any(p.requires_grad for p in dec.parameters())):
             srun = PassRun(eng, qconst, None, coords[0].contiguous(), que_depth[0].detach().contiguous(), dec, agg,
-                           dec.cfg['use_vis'], dec.cfg['bias_val'], 0, 0, False)
+                           dec.cfg['use_vis'], dec.cfg['bias_val'], 0, 0, False, deterministic=self._deterministic_mode())
             return SelfHitFn.apply(srun, h, w, que_imgs_info['ray_feats'], *[p for _, p in srun.dist_params()])[None]
         feats = eng.interpolate_feats(que_imgs_info['ray_feats'], coords, h, w, align_corners=False)      # [1,rn,32]
         mean, var, vis, aw = eng.dist_decoder_rows(feats[0], packed if packed is not None else self._packed_pass(eng, is_fine),
@@ -211,6 +214,20 @@ class HipRenderPath:
             raise NotImplementedError("neuray_amd: cfg['hip_coarse_pass'] = 'visibility' lives in the fp32 library (hip_variant = %r)"
                                       % (cfg.get('hip_variant'),))
         return mode
+
+    def _deterministic_mode(self):
+        """cfg['hip_deterministic'] (False, True or 'auto' = torch.are_deterministic_algorithms_enabled(); NEURAY_HIP_DETERMINISTIC = 0 / 1
+        wins) -> bool: the training backward without float atomics.  The fused norm of the encoders and the depth-loss
+        path's stand-alone autograd functions read the process-wide switch fused_norm.deterministic(), into which this renderer's
+        value goes (RENDERER_DETERMINISTIC: the renderer that was constructed or rendered last).  The mode lives where the backward kernels live - the fp32 library and,
+        from the same sources, the split 'bf16x3' one; the inference-only 'bf16' library is refused here, before anything is launched."""
+        value = self.cfg.get('hip_deterministic', False)
+        on = fused_norm.resolve_deterministic(value)
+        if on and self.cfg.get('hip_variant', 'fp32') not in ('fp32', 'bf16x3'):
+            raise NotImplementedError("neuray_amd: cfg['hip_deterministic'] needs the backward kernels of the fp32 (or 'bf16x3') library; "
+                                      "hip_variant = %r is inference only" % (self.cfg.get('hip_variant'),))
+        fused_norm.RENDERER_DETERMINISTIC = value        # (the renderer's own slot of the process-wide switch; a user's DETERMINISTIC is not touched)
+        return on
 
     def _visibility_coarse(self, que_depth, que_imgs_info, ref_imgs_info):
         """The coarse pass of cfg['hip_coarse_pass'] = 'visibility': hit probabilities of the coarse samples from the input views'
@@ -269,6 +286,7 @@ class HipRenderPath:
                 outs.append(self.render_impl(sub, ref_imgs_info, is_train))
             return {k: torch.cat([o[k] for o in outs], 0) for k in outs[0]}
         visibility = self._coarse_pass_mode() == 'visibility'
+        self._deterministic_mode()                           # (refuses what the mode cannot serve before the first launch)
         eng = self.engine(coords.device)
         rn = coords.shape[1]
         # the fine-sampling uniforms (render_ops.py:205: torch.rand on the CPU generator, the only draw of render_impl) are taken

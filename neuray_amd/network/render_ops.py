@@ -71,20 +71,22 @@ def depth2inv_dists(depth, depth_range):
 
 class _InterpFn(torch.autograd.Function):
     """interpolate_feats with the gradient w.r.t. the feature map (the coordinates are constants on every call site of the
-    render / depth-loss path, renderer.py:127-155,282-300)."""
+    render / depth-loss path, renderer.py:127-155,282-300).  The backward follows the process-wide deterministic switch
+    (fused_norm.deterministic()) as it stands at the forward: on, the scatter is the sorted segmented sum, no atomics."""
 
     @staticmethod
     def forward(ctx, feats, coords, mask, h, w, align):
         eng = engine_for(feats.device)
         ctx.save_for_backward(coords, mask)
-        ctx.meta = (eng, tuple(feats.shape), h, w, align)
+        from . import fused_norm
+        ctx.meta = (eng, tuple(feats.shape), h, w, align, fused_norm.deterministic())
         return eng.interpolate_feats(feats, coords, h, w, align_corners=align, mask=mask)
 
     @staticmethod
     def backward(ctx, d_out):
         coords, mask = ctx.saved_tensors
-        eng, shape, h, w, align = ctx.meta
-        return eng.interpolate_feats_backward(d_out.contiguous(), shape, coords, h, w, align_corners=align, mask=mask), \
+        eng, shape, h, w, align, det = ctx.meta
+        return eng.interpolate_feats_backward(d_out.contiguous(), shape, coords, h, w, align_corners=align, mask=mask, deterministic=det), \
             None, None, None, None, None
 
 

@@ -52,6 +52,10 @@ class NeuralRayBaseRenderer(HipRenderPath, nn.Module):
         # network runs on the fine samples only, there is no 'pixel_colors_nr'.  Inference only, needs use_hierarchical_sampling
         # (DESIGN.md section 4.17).  The environment variable NEURAY_HIP_COARSE wins.
         'hip_coarse_pass': 'network',
+        # not a reference key: False / True / 'auto' (= torch.are_deterministic_algorithms_enabled()): the training backward - and the fused
+        # norm's statistics - without float atomics, every sum in a stated order: gradients bitwise reproducible from run to run (DESIGN.md
+        # section 4.18).  Off by default (a sort and extra scratch per pass).  The environment variable NEURAY_HIP_DETERMINISTIC = 0 / 1 wins.
+        'hip_deterministic': False,
         # not a reference key: the inference packs carry prob_embed.2 folded into its consumers neuray_fc.0 / base_fc.0 (one 32 x 32
         # layer less per (point, view); the same function up to fp32 rounding - neuray_pack_pass_weights_folded)
         'hip_fold_prob_embed': True,
@@ -77,6 +81,7 @@ class NeuralRayBaseRenderer(HipRenderPath, nn.Module):
         self._engine = None
         self._engine_test_lib = None     # CPU test-suite hook (emulator build of the kernels)
         self._packed = {}
+        self._deterministic_mode()       # (validates cfg['hip_deterministic'] and hands it to the encoders' fused norm before the first encode_views)
 
     def encode_views(self, imgs, ray_feats):
         """renderer.py:229-235: image_encoder, then vis_encoder on its output -> (img_feats, refined ray_feats).
