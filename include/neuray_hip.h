@@ -675,6 +675,29 @@ int neuray_inorm_backward_det(const float* x_dev, const float* out_padded_dev, l
                               int act, float* partials_dev, float* raw_dev, float* dx_dev, float* d_res_dev, float* d_gamma_dev,
                               float* d_beta_dev, void* stream);
 
+/* ---- procedural 3-D scenes (neuray_amd/procedural.py; added within ABI 11: everything above is unchanged).  A ray caster
+ * for up to NEURAY_PROC_MAX_PRIMS spheres and axis-aligned boxes: posed ground truth (colour, exact z-depth, mask, primitive index) to train
+ * and evaluate on.  scene_dev [NEURAY_PROC_HEADER + n_prims * NEURAY_PROC_PRIM] floats: header = n_prims, unit light direction (3), ambient,
+ * background colour (3), 8 zeros; primitive = kind (0 sphere, 1 box), centre (3), half-extents (3; a sphere's radius first), base colour
+ * (3), specular strength, exponent, 4 texture waves of (k (3, cycles per unit), phase, amplitude (3)), 8 zeros.  A ray of pixel (x, y) with
+ * sub-sample offset (ox, oy): origin -R^T t, direction R^T K^-1 [x + ox, y + oy, 1]^T, un-normalised, so that the ray parameter is the z-depth.
+ * ss sub-rays per axis (1 .. 4) at offsets (i + 1/2) / ss - 1/2; the colour is their mean, depth / mask / prim are the centre ray's (depth 0,
+ * mask 0, prim -1 on a miss).  depth_dev, mask_dev and prim_dev may be NULL. */
+#define NEURAY_PROC_HEADER 16
+#define NEURAY_PROC_PRIM 48
+#define NEURAY_PROC_MAX_PRIMS 32
+typedef struct NeurayProceduralArgs {
+    const float* scene_dev;
+    const float* poses_dev;            /* [n][3][4] world -> camera */
+    const float* Ks_inv_dev;           /* [n][3][3] */
+    float* rgb_dev;                    /* [n][3][h][w] */
+    float* depth_dev;                  /* [n][h][w] */
+    unsigned char* mask_dev;           /* [n][h][w] */
+    signed char* prim_dev;             /* [n][h][w] */
+    int n_prims, n, h, w, ss, reserved;
+} NeurayProceduralArgs;
+int neuray_procedural_render(const NeurayProceduralArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

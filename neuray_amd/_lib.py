@@ -98,6 +98,12 @@ class NeurayVisibilityArgs(C.Structure):
         [('var_bias', C.c_float), ('ground', C.c_float), ('alpha_dev', C.c_void_p), ('nvalid_dev', C.c_void_p)]
 
 
+class NeurayProceduralArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('scene_dev', 'poses_dev', 'Ks_inv_dev', 'rgb_dev', 'depth_dev', 'mask_dev', 'prim_dev')] + \
+        [(n, C.c_int) for n in ('n_prims', 'n', 'h', 'w', 'ss', 'reserved')]
+
+
+PROC_HEADER, PROC_PRIM, PROC_MAX_PRIMS = 16, 48, 32   # the scene array of neuray_procedural_render (include/neuray_hip.h NEURAY_PROC_*)
 LOSS_RENDER, LOSS_CONSIST, LOSS_DEPTH = 0, 1, 2   # NeurayLossTerm.kind (include/neuray_hip.h NEURAY_LOSS_*)
 LOSS_MAX_TERMS = 4
 DET_POINTS, DET_RAYS, DET_SELF_HIT, DET_ROWS = 0, 1, 2, 3   # neuray_deterministic_partials_floats (include/neuray_hip.h NEURAY_DET_*)
@@ -229,6 +235,8 @@ SYMBOLS = {
     'neuray_interpolate_feats_backward_sorted': (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 2),
     'neuray_inorm_chunks': (C.c_int, [C.c_int] * 4),
     'neuray_inorm_forward_det': (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] * 3 + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p]),
+    # procedural scenes
+    'neuray_procedural_render': (C.c_int, [C.POINTER(NeurayProceduralArgs), C.c_void_p]),
     'neuray_inorm_backward_det': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 7),
 }
 

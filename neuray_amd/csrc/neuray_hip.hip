@@ -9,6 +9,7 @@
 #include "nr_kernels_metrics.h"
 #include "nr_kernels_loss.h"
 #include "nr_kernels_lpips.h"
+#include "nr_kernels_proc.h"
 // the plain bf16-operand build is inference only; the fp32 build and the split build (hi + lo bf16 operands: fp32-grade products)
 // carry the training path
 #if defined(NR_BF16_QUADS) && !defined(NR_BF16_SPLIT)
@@ -61,6 +62,7 @@ static_assert(NEURAY_PASS_TENSORS == nr::T_COUNT, "abi");
 static_assert(NEURAY_DBG_FIELDS == nr::kDbgFields, "abi");
 static_assert(NEURAY_RAY_ATT_SAVE == nr::kRayAttSave, "abi");
 static_assert(NEURAY_MAX_SAMPLES == nr::kMaxSamples, "abi");
+static_assert(NEURAY_PROC_HEADER == nr::kProcHeader && NEURAY_PROC_PRIM == nr::kProcPrim && NEURAY_PROC_MAX_PRIMS == nr::kProcMaxPrims, "abi");
 
 template <int NT, int VPW, bool HAS_VIS, int OWN, int MINW, bool SAVE = false, int AR = nr::AR_F32>
 int launch_points_own(const nr::PointParams& p, void* stream) {
@@ -1410,6 +1412,22 @@ int neuray_visibility_rays(const float* alpha, const int* nvalid, int rn, int dn
     NR_LAUNCH(nr::vis_rays_kernel, dim3(grid), dim3(64), 0, stream, alpha, nvalid, rn, dn, view_num, point_num, hit_prob, ray_mask);
     return check_launch("neuray_visibility_rays");
 #endif
+}
+
+int neuray_procedural_render(const NeurayProceduralArgs* a, void* stream) {
+    if (!a) return fail("neuray_procedural_render: null args");
+    if (a->ss < 1 || a->ss > 4) return fail("neuray_procedural_render: ss=%d outside [1,4]", a->ss);
+    if (a->n_prims < 0 || a->n_prims > NEURAY_PROC_MAX_PRIMS) return fail("neuray_procedural_render: n_prims=%d outside [0,%d]", a->n_prims, NEURAY_PROC_MAX_PRIMS);
+    if (a->n < 1 || a->h < 1 || a->w < 1) return fail("neuray_procedural_render: bad size n=%d h=%d w=%d", a->n, a->h, a->w);
+    if (a->n > 65535 || (a->h + nr::kProcTileY - 1) / nr::kProcTileY > 65535) return fail("neuray_procedural_render: n=%d h=%d too large for one call", a->n, a->h);
+    if (!a->scene_dev || !a->poses_dev || !a->Ks_inv_dev || !a->rgb_dev) return fail("neuray_procedural_render: scene / poses / Ks_inv / rgb missing");
+    nr::ProcParams p;
+    p.scene = a->scene_dev; p.poses = a->poses_dev; p.Ks_inv = a->Ks_inv_dev;
+    p.rgb = a->rgb_dev; p.depth = a->depth_dev; p.mask = a->mask_dev; p.prim = a->prim_dev;
+    p.n_prims = a->n_prims; p.n = a->n; p.h = a->h; p.w = a->w; p.ss = a->ss;
+    const dim3 grid((unsigned)((a->w + nr::kProcTileX - 1) / nr::kProcTileX), (unsigned)((a->h + nr::kProcTileY - 1) / nr::kProcTileY), (unsigned)a->n);
+    NR_LAUNCH(nr::procedural_render_kernel, grid, dim3(nr::kProcTileX * nr::kProcTileY), 0, stream, p);
+    return check_launch("neuray_procedural_render");
 }
 
 #ifdef NR_B2_PROFILE

@@ -381,6 +381,9 @@ def get_database_split(database, split_type='val'):
     elif name.startswith('dtu_test'):
         val_ids = database.get_img_ids()[3:-3:8]
         train_ids = [i for i in database.get_img_ids(check_depth_exist=depth_valid) if i not in val_ids]
+    elif name.startswith('procedural'):           # (no counterpart in the reference: every 8th view held out, the LLFF rule)
+        val_ids = database.get_img_ids()[::8]
+        train_ids = [i for i in database.get_img_ids(check_depth_exist=depth_valid) if i not in val_ids]
     else:
         raise NotImplementedError(name)
     return train_ids, val_ids
@@ -395,3 +398,6 @@ def prepare_eval_render(database, use_depth=True):
     que_shapes = np.asarray([database.get_image(i).shape[:2] for i in render_ids], np.int64)
     que_depth_ranges = np.asarray([database.get_depth_range(i) for i in render_ids], np.float32)
     return que_poses, que_Ks, que_shapes, que_depth_ranges, ref_ids, render_ids
+
+
+from . import procedural  # noqa: E402,F401  (registers 'procedural/<seed>/<white|black>_<size>' in name2database; at the end: it imports this module)

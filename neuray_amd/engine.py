@@ -967,6 +967,35 @@ class RenderEngine:
         self._event_done(ev, 'vis_rays', rn * dn)
         return {'hit_prob': hit, 'alpha': alpha, 'ray_mask': mask.bool(), 'nvalid': nvalid}
 
+    def procedural_render(self, scene, poses, Ks, h, w, ss=1, Ks_inv=None, outputs=('depth', 'mask', 'prim'), n_prims=None):
+        """Ray-cast a procedural scene (neuray_amd/procedural.py) from n cameras -> dict of device tensors: rgb [n,3,h,w]
+        float32 and, as named in `outputs`, depth [n,h,w] float32 (z-depth, 0 on a miss), mask [n,h,w] uint8, prim [n,h,w] int8 (-1 on a
+        miss).  scene: the flat array (numpy or tensor), poses [n,3,4], Ks [n,3,3]; K^-1 is host_inverse(Ks) unless the caller hands over
+        `Ks_inv` (a data pipeline that made it before the upload: no device -> host copy then)."""
+        scene = self._f32(torch.as_tensor(scene)).reshape(-1)
+        poses = self._f32(torch.as_tensor(poses)).reshape(-1, 3, 4)
+        n = poses.shape[0]
+        if Ks_inv is None:
+            Ks_inv = host_inverse(torch.as_tensor(Ks).reshape(-1, 3, 3))
+        Ks_inv = self._f32(torch.as_tensor(Ks_inv)).reshape(-1, 3, 3)
+        assert Ks_inv.shape[0] == n
+        if n_prims is None:
+            n_prims, rest = divmod(scene.numel() - _lib.PROC_HEADER, _lib.PROC_PRIM)
+            assert rest == 0 and n_prims >= 0, "scene array: %d floats" % scene.numel()
+        assert scene.numel() >= _lib.PROC_HEADER + int(n_prims) * _lib.PROC_PRIM or n_prims > _lib.PROC_MAX_PRIMS
+        size = (n, max(int(h), 0), max(int(w), 0))
+        out = {'rgb': self.empty(n, 3, size[1], size[2])}
+        for k, dt in (('depth', torch.float32), ('mask', torch.uint8), ('prim', torch.int8)):
+            if k in outputs:
+                out[k] = self.empty(*size, dtype=dt)
+        ptr = lambda k: out[k].data_ptr() if k in out else None     # noqa: E731
+        a = _lib.NeurayProceduralArgs(scene.data_ptr(), poses.data_ptr(), Ks_inv.data_ptr(), out['rgb'].data_ptr(), ptr('depth'), ptr('mask'),
+                                      ptr('prim'), int(n_prims), n, int(h), int(w), int(ss), 0)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_procedural_render(C.byref(a), self._stream()))
+        self._event_done(ev, 'procedural', n * int(h) * int(w))
+        return out
+
     def direct_render_rays_backward(self, alpha, colors, d_pixel, d_hit_prob=None):
         """Backward of direct_render's ray kernel: alpha [rn,dn] (logits), colors [rn,dn,3] (the SH colours), d_pixel [rn,3], d_hit_prob
         [rn,dn] or None -> (d_alpha [rn,dn], d_colors [rn,dn,3])"""

@@ -1,0 +1,185 @@
+"""Procedural ground truth at work: what the ray-cast kernel costs, and a first look at image quality against
+ground truth - a NeuralRayFtRenderer trained from scratch on one procedural scene, its held-out views rendered in three modes.
+
+    python tools/train_procedural.py --time
+        kernel time (device events, median of 20 after warm-up) of one ProceduralStream batch - 13 views of 416 x 608, ss 1 and 2 - and of
+        one 800 x 800 view, and the generalisation step of bench.gen_train_case fed by its fixed batch against the same step fed by the
+        stream, in one process.  One JSON line.
+    python tools/train_procedural.py --scene procedural/0/white_800 --steps N
+        trains every network of a NeuralRayFtRenderer on the scene's 42 training views (render + consistency loss of neuray_amd.loss, Adam),
+        then renders the 6 held-out views with hip_arith f32 / x3 and the network coarse pass, and x3 with hip_coarse_pass = 'visibility':
+        PSNR / SSIM (engine.image_metrics) against the ray-cast images and the rendered depth against the true depth.  One JSON line.
+
+These numbers are about ONE procedurally generated scene and a model trained from scratch for minutes - not the paper's checkpoints."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from neuray_amd import database, pipeline, procedural  # noqa: E402
+from neuray_amd.loss import name2loss, total_loss  # noqa: E402
+from neuray_amd.network import render_ops  # noqa: E402
+
+
+def median_ms(fn, reps=20, warmup=3):
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return float(np.median(times))
+
+
+def kernel_times(dev):
+    eng = render_ops.engine_for(dev)
+    res = {}
+    from neuray_amd.engine import host_inverse
+    scene = procedural.make_scene(1)
+    t_scene = torch.from_numpy(scene).to(dev)
+    for tag, n, h, w in (('stream_batch_13x416x608', 13, 416, 608), ('one_view_800x800', 1, 800, 800)):
+        t_poses = torch.from_numpy(procedural.ring_cameras(np.random.RandomState(1), n)).to(dev)
+        Ks_inv = host_inverse(torch.from_numpy(procedural.intrinsics(h, w)[None])).repeat(n, 1, 1).to(dev)
+        for ss in (1, 2):
+            res['%s_ss%d_ms' % (tag, ss)] = median_ms(lambda: eng.procedural_render(t_scene, t_poses, None, h, w, ss, Ks_inv=Ks_inv,
+                                                                                    outputs=('depth', 'mask')))
+    res['prims'] = procedural.scene_prims(scene)
+    return res
+
+
+def gen_step_times(dev, steps=10):
+    """bench.gen_train_case's loop on its fixed batch, then the same model / optimiser / losses on a fresh stream batch per step"""
+    import bench
+    model, opt, step = bench.gen_train_case(dev, host_ks_inv=True)
+    rfn, h, w = 8, 416, 608
+
+    def timed(fn):
+        for _ in range(6):
+            fn()
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize(dev)
+        return 1e3 * (time.perf_counter() - t0) / steps
+    fixed = timed(step)
+    stream = procedural.ProceduralStream(dev, seed=0, h=h, w=w, rfn=rfn, extra_src=4, rays=512)
+
+    def stream_step():
+        batch = next(stream)
+        ref = batch['ref_imgs_info']
+        opt.zero_grad(set_to_none=True)
+        out = model({k: dict(v) if isinstance(v, dict) else v for k, v in batch.items()})
+        gt = out['pixel_colors_gt']
+        loss = ((out['pixel_colors_nr'] - gt) ** 2).mean() + ((out['pixel_colors_nr_fine'] - gt) ** 2).mean()
+        c = out['depth_coords'].long()
+        d = ref['true_depth'][torch.arange(rfn, device=dev)[:, None], 0, c[..., 1].clamp(max=h - 1), c[..., 0].clamp(max=w - 1)]
+        near, far = -1 / ref['depth_range'][:, 0:1], -1 / ref['depth_range'][:, 1:2]
+        d = (((-1 / d.clamp(min=1e-5)) - near) / (far - near)).clamp(0, 1)
+        loss = loss + ((d - out['depth_mean']) ** 2).mean() + ((d - out['depth_mean_fine']) ** 2).mean()
+        loss.backward()
+        opt.step()
+    streamed = timed(stream_step)
+    render_ops.check_deferred_inputs(dev, wait=True)
+    return {'gen_step_fixed_batch_ms': fixed, 'gen_step_stream_ms': streamed}
+
+
+def evaluate(ft, db, val_ids, dev):
+    """the held-out views in the three modes -> {mode: {psnr, ssim, depth_abs_err, ms_per_image}}"""
+    modes = (('f32_network', 'f32', 'network'), ('x3_network', 'x3', 'network'), ('x3_visibility', 'x3', 'visibility'))
+    gt = ft.val_imgs_info['imgs'].to(dev)
+    n, _, h, w = gt.shape
+    true_depth = torch.from_numpy(np.stack([db.get_depth(i) for i in val_ids])).to(dev)
+    mask = torch.from_numpy(np.stack([db.get_mask(i) for i in val_ids])).to(dev)
+    res = {}
+    ft.eval()
+    for tag, arith, coarse in modes:
+        ft.cfg['hip_arith'], ft.cfg['hip_coarse_pass'] = arith, coarse
+        ft.__dict__['_engine'] = None                      # the next render builds the engine of this arithmetic
+        eng = render_ops.engine_for(dev)
+        psnr, ssim, derr, ms = [], [], [], []
+        for vi in range(n):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                out = ft({'index': vi, 'eval': True})
+            torch.cuda.synchronize(dev)
+            ms.append(1e3 * (time.perf_counter() - t0))
+            m = eng.image_metrics(out['pixel_colors_nr_fine'].reshape(1, h * w, 3).contiguous(),
+                                  gt[vi].permute(1, 2, 0).reshape(1, h * w, 3).contiguous(), h, w)
+            psnr.append(float(m['psnr'][0]))
+            ssim.append(float(m['ssim'][0]))
+            rd = out.get('render_depth_fine', out.get('render_depth'))
+            if rd is not None:
+                rd = rd.reshape(h, w)
+                derr.append(float((rd - true_depth[vi]).abs()[mask[vi]].mean()))
+        res[tag] = {'psnr': float(np.mean(psnr)), 'ssim': float(np.mean(ssim)), 'depth_abs_err': float(np.mean(derr)) if derr else None,
+                    'ms_per_image': float(np.median(ms))}
+    return res
+
+
+def train(args, dev):
+    db = database.parse_database_name(args.scene)
+    train_ids, val_ids = database.get_database_split(db, 'val_all')
+    t0 = time.perf_counter()
+    scene = {'ref_imgs_info': pipeline.build_imgs_info(db, train_ids), 'val_imgs_info': pipeline.build_imgs_info(db, val_ids), 'database': db}
+    t_data = time.perf_counter() - t0
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    from neuray_amd.network.renderer import NeuralRayFtRenderer
+    cfg = {'use_hierarchical_sampling': True, 'use_self_hit_prob': True, 'render_depth': True, 'use_validation': True,
+           'ray_feats_res': [db.h // 4, db.w // 4], 'train_ray_num': args.rays}
+    ft = NeuralRayFtRenderer(cfg, scene=scene).train().to(dev)
+    opt = torch.optim.Adam(ft.parameters(), lr=args.lr)
+    losses = [name2loss['render']({'use_nr_fine_loss': True}), name2loss['consist']({})]
+    curve = []
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    for step in range(args.steps):
+        opt.zero_grad(set_to_none=True)
+        out = ft({})
+        loss, log = total_loss(losses, out, {}, step)
+        loss.backward()
+        opt.step()
+        if step % max(args.steps // 10, 1) == 0 or step == args.steps - 1:
+            curve.append((step, float(log['loss_rgb_nr_fine'].mean())))
+    torch.cuda.synchronize(dev)
+    t_train = time.perf_counter() - t0
+    res = {'scene': args.scene, 'rendered_on': db.rendered_on, 'views_train': len(train_ids), 'views_test': len(val_ids), 'steps': args.steps,
+           'rays_per_step': args.rays, 'lr': args.lr, 'data_s': t_data, 'train_s': t_train, 'ms_per_step': 1e3 * t_train / max(args.steps, 1),
+           'loss_rgb_nr_fine': curve, 'modes': evaluate(ft, db, val_ids, dev),
+           'what': 'one procedurally generated scene, every network trained from scratch for minutes: not the paper\'s checkpoints'}
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--time', action='store_true')
+    ap.add_argument('--scene', default='procedural/0/white_800')
+    ap.add_argument('--steps', type=int, default=2000)
+    ap.add_argument('--rays', type=int, default=512)
+    ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--seed', type=int, default=0)
+    args = ap.parse_args()
+    dev = torch.device('cuda:0')
+    if args.time:
+        res = kernel_times(dev)
+        res.update(gen_step_times(dev))
+    else:
+        res = train(args, dev)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
