@@ -630,7 +630,8 @@ int neuray_visibility_rays(const float* alpha_dev, const int* nvalid_dev, int rn
  * caller sorts (e.g. torch.sort(stable=True)) between the two calls and passes the sorted keys and the permutation.  For one library, one
  * device model and identical inputs the results are bitwise reproducible; they are not bitwise those of the atomic entry points.
  * neuray_deterministic_partials_floats(kernel, rn, dn): floats of the partials buffer of a NEURAY_DET_* kernel (ROWS: rn = rows, dn unused).
- * The *_det entries take the arguments of their namesakes plus the scratch; buffers named `zeroed` must be zero on entry. */
+ * Each *_det entry is its namesake's launcher with scratch: the same arguments, checks, grid and kernel (instantiated without atomics), plus
+ * the scratch buffers, which must not be NULL; buffers named `zeroed` must be zero on entry. */
 #define NEURAY_DET_POINTS 0
 #define NEURAY_DET_RAYS 1
 #define NEURAY_DET_SELF_HIT 2

@@ -55,6 +55,23 @@ int grid_for(long long work_items, int per_block, int max_blocks) {
     return (int)b;
 }
 
+// Kernels with dynamic LDS.  A kernel may use more than 64 KB only after its limit was raised; that call costs host time on every launch,
+// so launch_lds makes it past 64 KB only, or - `always` - where a site's kernel is known to be above it.  The kernel arrives as a function
+// pointer: the emulator's NR_LAUNCH calls it inside a [=] lambda.
+template <class K>
+void allow_lds(K k, size_t smem) {
+#ifndef NEURAY_EMU
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+#else
+    (void)k; (void)smem;
+#endif
+}
+template <class K, class P>
+void launch_lds(K k, dim3 grid, dim3 block, size_t smem, void* stream, const P& p, bool always = false) {
+    if (always || smem > 64 * 1024) allow_lds(k, smem);
+    NR_LAUNCH(k, grid, block, smem, stream, p);
+}
+
 static_assert(NEURAY_POINT_REC == nr::kPointRec, "abi");
 static_assert(NEURAY_VIEW_CONST == nr::kViewConst, "abi");
 static_assert(NEURAY_QUERY_CONST == nr::kQueryConst, "abi");
@@ -92,10 +109,7 @@ int launch_points_own(const nr::PointParams& p, void* stream) {
     } else if (p.dbg) {
         return fail("neuray_render_points: dbg_dev and saved_dev together are not built (run the pass twice)");
     }
-#ifndef NEURAY_EMU
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-    NR_LAUNCH(k, dim3(grid), dim3(threads), smem, stream, p);
+    launch_lds(k, dim3(grid), dim3(threads), smem, stream, p);
     return check_launch("neuray_render_points");
 }
 
@@ -156,11 +170,8 @@ void launch_conv2d_x3(const nr::Conv2dX3Params& p, int bands, void* stream) {
     const long long q = (long long)p.n * hp * lw;
     const int per = nr::kC2Waves * NT * 16;
     const size_t smem = (size_t)nr::conv2d_x3_smem_bytes(NT, lw);
-    auto k = nr::conv2d_x3_kernel<NT, MTW, WC, RELU>;
-#ifndef NEURAY_EMU
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-    NR_LAUNCH(k, dim3((unsigned)((q + per - 1) / per), (unsigned)(p.cout / 16 / MTW / WC), (unsigned)bands), dim3(64 * nr::kC2Waves * WC), smem, stream, p);
+    launch_lds(nr::conv2d_x3_kernel<NT, MTW, WC, RELU>, dim3((unsigned)((q + per - 1) / per), (unsigned)(p.cout / 16 / MTW / WC), (unsigned)bands),
+               dim3(64 * nr::kC2Waves * WC), smem, stream, p);
 }
 int g_conv2d_nt = 0, g_conv2d_mtw = 0, g_conv2d_tw = 0, g_conv2d_wc = 0;     // NEURAY_CONV2D_NT / _MTW / _TW / _WC: tile-shape overrides of the A/B tools
 }  // namespace
@@ -309,17 +320,10 @@ int neuray_render_rays(const NeurayRaysArgs* a, void* stream) {
     const size_t smem = nr::ray_smem_bytes(a->dn, rpw);
     if (smem > 160 * 1024) return fail("neuray_render_rays: dn=%d needs %zu bytes of LDS", a->dn, smem);
     const int grid = grid_for(a->rn, nr::kRayWaves * rpw, 256 * 16);
-    auto launch = [&](auto k) {
-#ifndef NEURAY_EMU
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-        NR_LAUNCH(k, dim3(grid), dim3(64 * nr::kRayWaves), smem, stream, p);
-    };
-    if (a->att_save_dev) {                                 // training forward: the attention's softmax statistics are kept for the backward
-        if (rpw == 2) launch(nr::rays_kernel<true, 2>); else launch(nr::rays_kernel<true, 1>);
-    } else {
-        if (rpw == 2) launch(nr::rays_kernel<false, 2>); else launch(nr::rays_kernel<false, 1>);
-    }
+    // (saved: the training forward - the attention's softmax statistics are kept for the backward)
+    const auto k = a->att_save_dev ? (rpw == 2 ? nr::rays_kernel<true, 2> : nr::rays_kernel<true, 1>)
+                                   : (rpw == 2 ? nr::rays_kernel<false, 2> : nr::rays_kernel<false, 1>);
+    launch_lds(k, dim3(grid), dim3(64 * nr::kRayWaves), smem, stream, p);
     return check_launch("neuray_render_rays");
 }
 
@@ -373,11 +377,7 @@ int neuray_conv3d_c32_c8(const float* x_ndhwc, const float* wpack, const float* 
     const long long strips = (long long)n * d * ((h + 1) / 2) * ((w + 15) / 16);       // a wave takes two output rows of a 16-voxel strip
     const int grid = grid_for(strips, nr::kConv0Waves, 256 * 8);
     const size_t smem = sizeof(float) * nr::kConv0PackFloats;                            // 72 KB: two workgroups per CU
-    auto k = nr::costreg_conv0_kernel;
-#ifndef NEURAY_EMU
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-    NR_LAUNCH(k, dim3(grid), dim3(64 * nr::kConv0Waves), smem, stream, p);
+    launch_lds(nr::costreg_conv0_kernel, dim3(grid), dim3(64 * nr::kConv0Waves), smem, stream, p, true);
     return check_launch("neuray_conv3d_c32_c8");
 }
 
@@ -484,11 +484,7 @@ int neuray_conv3x3_x3_wrw(const float* dy, const float* xp, int n, int cin, int 
     p.ksplit = conv2d_wrw_ksplit(n, cin, cout, hp, wp);
     const int pairs = (cin / 32) * (cout / 32);
     const size_t smem = sizeof(float) * 2 * nr::kWrwAcc * 64;
-    auto k = nr::conv2d_x3_wrw_kernel;
-#ifndef NEURAY_EMU
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-    NR_LAUNCH(k, dim3((unsigned)p.ksplit, (unsigned)pairs), dim3(256), smem, stream, p);
+    launch_lds(nr::conv2d_x3_wrw_kernel, dim3((unsigned)p.ksplit, (unsigned)pairs), dim3(256), smem, stream, p, true);
     NR_LAUNCH(nr::conv2d_x3_wrw_reduce_kernel, dim3((unsigned)(pairs * nr::kWrwAcc)), dim3(64 * nr::kWrwRedWaves), 0, stream, p);
     return check_launch("neuray_conv3x3_x3_wrw");
 }
@@ -579,50 +575,103 @@ int neuray_warp_variance_layout(const float* ref_feats, const float* src_feats, 
 }
 
 // ---- fused InstanceNorm + activation (+ residual) + reflection pad of the per-image encoders (nr_kernels_norm.h) ----------------
+// One launcher per direction.  `who` is the exported symbol the caller invoked; `partials` selects the form: NULL = the atomic statistics
+// (raw zeroed by the caller), else the deterministic ones (every workgroup's pair to partials, inorm_finish_kernel adds
+// them into raw in workgroup order).
 namespace {
 int norm_chunks(int planes, int hw) {          // workgroups per plane: ~4096 workgroups in all (16 per CU), each thread >= 4 elements
     int want = (4096 + planes - 1) / planes, most = (hw + 1023) / 1024;
     if (want > most) want = most;
     return want < 1 ? 1 : want;
 }
+
+// the shape and stride check of the four norm entries (a stride of 0 = dense images)
+int norm_check(const char* who, int n, int c, int h, int w, int pad, int act, long long stride_a, long long stride_b) {
+    if (n < 1 || c < 1 || h < 1 || w < 1 || pad < 0 || pad >= h || pad >= w || act < 0 || act > 2 || (long long)(h + 2 * pad) * (w + 2 * pad) >= (1 << 23))
+        return fail("%s: bad arguments n=%d c=%d h=%d w=%d pad=%d act=%d", who, n, c, h, w, pad, act);
+    const long long img = (long long)c * (h + 2 * pad) * (w + 2 * pad);
+    if ((stride_a != 0 && stride_a < img) || (stride_b != 0 && stride_b < img))
+        return fail("%s: image strides %lld / %lld < %lld", who, stride_a, stride_b, img);
+    return 0;
+}
+
+void norm_finish(const float* partials, int planes, int chunks, float* raw, void* stream) {
+    NR_LAUNCH(nr::inorm_finish_kernel, dim3((2 * planes + 255) / 256), dim3(256), 0, stream, partials, planes, chunks, raw);
+}
+
+int inorm_forward(const char* who, const float* x, const float* gamma, const float* beta, const float* res, long long res_stride_n,
+                  long long res_stride_c, long long res_stride_h, int n, int c, int h, int w, int pad, int act, float eps, float* partials,
+                  float* raw, float* stats, float* out_padded, long long out_stride_n, void* stream) {
+    if (!x || !gamma || !beta || !raw || !stats || !out_padded) return fail("%s: null pointer", who);
+    if (int rc = norm_check(who, n, c, h, w, pad, act, out_stride_n, 0)) return rc;
+    const long long img = (long long)c * (h + 2 * pad) * (w + 2 * pad);
+    const int planes = n * c, hw = h * w, chunks = norm_chunks(planes, hw);
+    if (partials) {
+        NR_LAUNCH(nr::inorm_stats_kernel<true>, dim3(chunks, planes), dim3(256), 0, stream, x, hw, partials);
+        norm_finish(partials, planes, chunks, raw, stream);
+    } else {
+        NR_LAUNCH(nr::inorm_stats_kernel<false>, dim3(chunks, planes), dim3(256), 0, stream, x, hw, raw);
+    }
+    nr::NormApplyParams p;
+    p.x = x; p.raw = raw; p.gamma = gamma; p.beta = beta; p.res = res; p.out = out_padded; p.stats = stats;
+    p.rs_n = res_stride_n; p.rs_c = res_stride_c; p.rs_h = res_stride_h; p.out_stride_n = out_stride_n ? out_stride_n : img;
+    p.n = n; p.c = c; p.h = h; p.w = w; p.pad = pad; p.act = act; p.eps = eps;
+    NR_LAUNCH(nr::inorm_apply_kernel, dim3(norm_chunks(planes, (h + 2 * pad) * (w + 2 * pad)), planes), dim3(256), 0, stream, p);
+    return check_launch(who);
+}
+
+int inorm_backward(const char* who, const float* x, const float* out_padded, long long out_stride_n, const float* d_out_padded,
+                   long long d_out_stride_n, const float* stats, const float* gamma, int n, int c, int h, int w, int pad, int act,
+                   float* partials, float* raw, float* dx, float* d_res, float* d_gamma, float* d_beta, void* stream) {
+    if (!x || !out_padded || !d_out_padded || !stats || !gamma || !raw || !dx) return fail("%s: null pointer", who);
+    if (int rc = norm_check(who, n, c, h, w, pad, act, out_stride_n, d_out_stride_n)) return rc;
+    const long long img = (long long)c * (h + 2 * pad) * (w + 2 * pad);
+    nr::NormBwdParams p;
+    p.x = x; p.out = out_padded; p.d_out = d_out_padded; p.stats = stats; p.gamma = gamma; p.dx = dx; p.d_res = d_res;
+    p.d_gamma = d_gamma; p.d_beta = d_beta; p.raw = partials ? partials : raw;
+    p.out_stride_n = out_stride_n ? out_stride_n : img; p.d_out_stride_n = d_out_stride_n ? d_out_stride_n : img;
+    p.n = n; p.c = c; p.h = h; p.w = w; p.pad = pad; p.act = act;
+    const int planes = n * c, hw = h * w, chunks = norm_chunks(planes, hw);
+    if (partials) {
+        NR_LAUNCH(nr::inorm_backward_reduce_kernel<true>, dim3(chunks, planes), dim3(256), 0, stream, p);
+        norm_finish(partials, planes, chunks, raw, stream);
+        p.raw = raw;
+    } else {
+        NR_LAUNCH(nr::inorm_backward_reduce_kernel<false>, dim3(chunks, planes), dim3(256), 0, stream, p);
+    }
+    NR_LAUNCH(nr::inorm_backward_apply_kernel, dim3(chunks, planes), dim3(256), 0, stream, p);
+    return check_launch(who);
+}
 }  // namespace
 
 int neuray_inorm_forward(const float* x, const float* gamma, const float* beta, const float* res, long long res_stride_n,
                          long long res_stride_c, long long res_stride_h, int n, int c, int h, int w, int pad, int act, float eps,
                          float* raw_zeroed, float* stats, float* out_padded, long long out_stride_n, void* stream) {
-    if (!x || !gamma || !beta || !raw_zeroed || !stats || !out_padded) return fail("neuray_inorm_forward: null pointer");
-    if (n < 1 || c < 1 || h < 1 || w < 1 || pad < 0 || pad >= h || pad >= w || act < 0 || act > 2 || (long long)(h + 2 * pad) * (w + 2 * pad) >= (1 << 23))
-        return fail("neuray_inorm_forward: bad arguments n=%d c=%d h=%d w=%d pad=%d act=%d", n, c, h, w, pad, act);
-    const long long img = (long long)c * (h + 2 * pad) * (w + 2 * pad);
-    if (out_stride_n != 0 && out_stride_n < img) return fail("neuray_inorm_forward: out_stride_n %lld < %lld", out_stride_n, img);
-    const int planes = n * c, hw = h * w;
-    NR_LAUNCH(nr::inorm_stats_kernel<false>, dim3(norm_chunks(planes, hw), planes), dim3(256), 0, stream, x, hw, raw_zeroed);
-    nr::NormApplyParams p;
-    p.x = x; p.raw = raw_zeroed; p.gamma = gamma; p.beta = beta; p.res = res; p.out = out_padded; p.stats = stats;
-    p.rs_n = res_stride_n; p.rs_c = res_stride_c; p.rs_h = res_stride_h; p.out_stride_n = out_stride_n ? out_stride_n : img;
-    p.n = n; p.c = c; p.h = h; p.w = w; p.pad = pad; p.act = act; p.eps = eps;
-    NR_LAUNCH(nr::inorm_apply_kernel, dim3(norm_chunks(planes, (h + 2 * pad) * (w + 2 * pad)), planes), dim3(256), 0, stream, p);
-    return check_launch("neuray_inorm_forward");
+    return inorm_forward("neuray_inorm_forward", x, gamma, beta, res, res_stride_n, res_stride_c, res_stride_h, n, c, h, w, pad, act, eps,
+                         nullptr, raw_zeroed, stats, out_padded, out_stride_n, stream);
+}
+
+int neuray_inorm_forward_det(const float* x, const float* gamma, const float* beta, const float* res, long long res_stride_n,
+                             long long res_stride_c, long long res_stride_h, int n, int c, int h, int w, int pad, int act, float eps,
+                             float* partials, float* raw, float* stats, float* out_padded, long long out_stride_n, void* stream) {
+    if (!partials) return fail("neuray_inorm_forward_det: null pointer");
+    return inorm_forward("neuray_inorm_forward_det", x, gamma, beta, res, res_stride_n, res_stride_c, res_stride_h, n, c, h, w, pad, act, eps,
+                         partials, raw, stats, out_padded, out_stride_n, stream);
 }
 
 int neuray_inorm_backward(const float* x, const float* out_padded, long long out_stride_n, const float* d_out_padded, long long d_out_stride_n,
                           const float* stats, const float* gamma, int n, int c, int h, int w, int pad, int act, float* raw_zeroed, float* dx,
                           float* d_res, float* d_gamma, float* d_beta, void* stream) {
-    if (!x || !out_padded || !d_out_padded || !stats || !gamma || !raw_zeroed || !dx) return fail("neuray_inorm_backward: null pointer");
-    if (n < 1 || c < 1 || h < 1 || w < 1 || pad < 0 || pad >= h || pad >= w || act < 0 || act > 2 || (long long)(h + 2 * pad) * (w + 2 * pad) >= (1 << 23))
-        return fail("neuray_inorm_backward: bad arguments n=%d c=%d h=%d w=%d pad=%d act=%d", n, c, h, w, pad, act);
-    const long long img = (long long)c * (h + 2 * pad) * (w + 2 * pad);
-    if ((out_stride_n != 0 && out_stride_n < img) || (d_out_stride_n != 0 && d_out_stride_n < img))
-        return fail("neuray_inorm_backward: image strides %lld / %lld < %lld", out_stride_n, d_out_stride_n, img);
-    nr::NormBwdParams p;
-    p.x = x; p.out = out_padded; p.d_out = d_out_padded; p.stats = stats; p.gamma = gamma; p.raw = raw_zeroed; p.dx = dx; p.d_res = d_res;
-    p.d_gamma = d_gamma; p.d_beta = d_beta;
-    p.out_stride_n = out_stride_n ? out_stride_n : img; p.d_out_stride_n = d_out_stride_n ? d_out_stride_n : img;
-    p.n = n; p.c = c; p.h = h; p.w = w; p.pad = pad; p.act = act;
-    const int planes = n * c, hw = h * w;
-    NR_LAUNCH(nr::inorm_backward_reduce_kernel<false>, dim3(norm_chunks(planes, hw), planes), dim3(256), 0, stream, p);
-    NR_LAUNCH(nr::inorm_backward_apply_kernel, dim3(norm_chunks(planes, hw), planes), dim3(256), 0, stream, p);
-    return check_launch("neuray_inorm_backward");
+    return inorm_backward("neuray_inorm_backward", x, out_padded, out_stride_n, d_out_padded, d_out_stride_n, stats, gamma, n, c, h, w, pad, act,
+                          nullptr, raw_zeroed, dx, d_res, d_gamma, d_beta, stream);
+}
+
+int neuray_inorm_backward_det(const float* x, const float* out_padded, long long out_stride_n, const float* d_out_padded, long long d_out_stride_n,
+                              const float* stats, const float* gamma, int n, int c, int h, int w, int pad, int act, float* partials, float* raw,
+                              float* dx, float* d_res, float* d_gamma, float* d_beta, void* stream) {
+    if (!partials) return fail("neuray_inorm_backward_det: null pointer");
+    return inorm_backward("neuray_inorm_backward_det", x, out_padded, out_stride_n, d_out_padded, d_out_stride_n, stats, gamma, n, c, h, w, pad,
+                          act, partials, raw, dx, d_res, d_gamma, d_beta, stream);
 }
 
 int neuray_upsample2x_pad_forward(const float* x, int planes, int h, int w, int pad, float scale_y, float scale_x, float* out_padded, void* stream) {
@@ -774,7 +823,7 @@ int neuray_points_resident_workgroups(int arith, int rfn) {
 #else
         auto k = nr::points_kernel<1, 2, false, 1, 512, NR_POINT_MINW_X3, false, false, nr::AR_X3>;
         const size_t smem = nr::point_smem_bytes<1>(4, nr::AR_X3);
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (smem > 64 * 1024) allow_lds(k, smem);
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 256, smem);
 #endif
     } else {
@@ -790,33 +839,49 @@ static_assert(NEURAY_PACKED_RAY_FLOATS == nr::kPackedRayFloats && NEURAY_RW_WQ =
               NEURAY_RW_OG0W == nr::RW_OG0W && NEURAY_RW_OG0B == nr::RW_OG0B && NEURAY_RW_OG2W == nr::RW_OG2W &&
               NEURAY_RW_OG2B == nr::RW_OG2B, "abi");
 
-int neuray_render_rays_backward(const NeurayRaysBwdArgs* a, void* stream) {
+// ---- one launcher per backward kernel.  Every backward kernel has two exported forms: the atomic one, and the deterministic one of
+// cfg['hip_deterministic'] (the kernel instantiated with DET = true stores every workgroup's sums with plain stores to
+// its row of a partials buffer, and reduce_partials adds the rows in workgroup order - no float atomics).  The *_det entry is its
+// namesake's launcher with scratch: `who` is the exported symbol the caller invoked, a NULL `partials` selects the atomic form.
+// neuray_deterministic_partials_floats sizes the partials by the grid helpers below: the launchers call the same ones.
+namespace {
+int rays_bwd_grid(int rn, int dn) { return grid_for(rn, nr::ray_bwd_waves(dn), 256 * 4); }      // (ray_bwd_waves: rays per workgroup)
+int points_bwd_grid(int rn, int dn) { return grid_for((long long)rn * dn, 16, 256); }           // persistent: one workgroup per CU
+int rows_bwd_grid(int n) { return grid_for(n, 16, 512); }                                       // the self-hit and the decoder-rows backward: a wave per 16 rows
+
+int reduce_partials(const char* who, const float* partials, int g, long long n, float* out, void* stream) {
+    NR_LAUNCH(nr::reduce_partials_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, partials, g, n, out);
+    return check_launch(who);
+}
+
+int rays_backward(const char* who, const NeurayRaysBwdArgs* a, float* partials, void* stream) {
     if (!a || !a->point_rec_dev || !a->depth_dev || !a->pos_enc_dev || !a->packed_weights_dev || !a->d_pixel_dev ||
         !a->d_point_rec_dev || !a->d_ray_weights_dev)
-        return fail("neuray_render_rays_backward: null argument");
-    if (a->rn < 1) return fail("neuray_render_rays_backward: rn=%d", a->rn);
-    if (a->dn < 3 || a->dn > NEURAY_MAX_SAMPLES) return fail("neuray_render_rays_backward: dn=%d outside [3,%d]", a->dn, NEURAY_MAX_SAMPLES);
+        return fail("%s: null argument", who);
+    if (a->rn < 1) return fail("%s: rn=%d", who, a->rn);
+    if (a->dn < 3 || a->dn > NEURAY_MAX_SAMPLES) return fail("%s: dn=%d outside [3,%d]", who, a->dn, NEURAY_MAX_SAMPLES);
+    const bool det = partials != nullptr;
     nr::RayBwdParams p;
     p.point_rec = a->point_rec_dev; p.depth = a->depth_dev; p.pos_enc = a->pos_enc_dev; p.weights = a->packed_weights_dev;
     p.d_pixel = a->d_pixel_dev; p.d_hit_prob = a->d_hit_prob_dev; p.d_depth = a->d_render_depth_dev;
-    p.d_point_rec = a->d_point_rec_dev; p.d_weights = a->d_ray_weights_dev; p.att_saved = a->att_saved_dev; p.rn = a->rn; p.dn = a->dn;
-    const size_t smem = nr::ray_bwd_smem_bytes(a->dn);
-    const int waves = nr::ray_bwd_waves(a->dn);            // rays per workgroup
-    const int grid = grid_for(a->rn, waves, 256 * 4);
-    if (a->dn <= 64) {
-        auto k = nr::rays_backward_kernel<1>;
-#ifndef NEURAY_EMU
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-        NR_LAUNCH(k, dim3(grid), dim3(64 * waves), smem, stream, p);
-    } else {                                               // two samples per lane
-        auto k = nr::rays_backward_kernel<2>;
-#ifndef NEURAY_EMU
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-        NR_LAUNCH(k, dim3(grid), dim3(64 * waves), smem, stream, p);
-    }
-    return check_launch("neuray_render_rays_backward");
+    p.d_point_rec = a->d_point_rec_dev; p.d_weights = det ? partials : a->d_ray_weights_dev; p.att_saved = a->att_saved_dev;
+    p.rn = a->rn; p.dn = a->dn;
+    const size_t smem = nr::ray_bwd_smem_bytes(a->dn, det);
+    const int waves = nr::ray_bwd_waves(a->dn), grid = rays_bwd_grid(a->rn, a->dn);
+    // one sample per lane up to 64 samples, two beyond
+    const auto k = a->dn <= 64 ? (det ? nr::rays_backward_kernel<1, true> : nr::rays_backward_kernel<1, false>)
+                               : (det ? nr::rays_backward_kernel<2, true> : nr::rays_backward_kernel<2, false>);
+    launch_lds(k, dim3(grid), dim3(64 * waves), smem, stream, p);
+    if (int rc = check_launch(who)) return rc;
+    return det ? reduce_partials(who, partials, grid, nr::kPackedRayFloats, a->d_ray_weights_dev, stream) : 0;
+}
+}  // namespace
+
+int neuray_render_rays_backward(const NeurayRaysBwdArgs* a, void* stream) { return rays_backward("neuray_render_rays_backward", a, nullptr, stream); }
+
+int neuray_render_rays_backward_det(const NeurayRaysBwdArgs* a, float* partials_dev, void* stream) {
+    if (!partials_dev) return fail("neuray_render_rays_backward_det: null argument");
+    return rays_backward("neuray_render_rays_backward_det", a, partials_dev, stream);
 }
 
 size_t neuray_flat_pass_floats(void) { return (size_t)nr::kFlatPassFloats; }
@@ -846,86 +911,146 @@ size_t neuray_points_backward_handover_floats(int npoints) {
 #endif
 }
 
-int neuray_render_points_backward(const NeurayPointsBwdArgs* a, void* stream) {
+namespace {
+// partials / rows / keys: the scratch of the deterministic form (all three, or none for the atomic one).  The deterministic instantiation
+// leaves the maps' gradients to neuray_points_backward_scatter: it does not read d_ray_feats / d_img_feats, and takes rows and keys in
+// those two fields of the parameter struct.
+int points_backward(const char* who, const NeurayPointsBwdArgs* a, float* partials, float* rows, int* keys, void* stream) {
+    const bool det = partials != nullptr;
     if (!a || !a->query_const_dev || !a->view_const_dev || !a->coords_dev || !a->depth_dev || !a->ray_feats_nhwc_dev ||
         !a->img_feats_nhwc_dev || !a->rgba_dev || !a->flat_weights_dev || !a->d_point_rec_dev || !a->d_flat_weights_dev ||
-        !a->d_ray_feats_nhwc_dev || !a->d_img_feats_nhwc_dev)
-        return fail("neuray_render_points_backward: null argument");
-    if (a->rfn < 1 || a->rfn > NEURAY_MAX_VIEWS) return fail("neuray_render_points_backward: rfn=%d outside [1,%d]", a->rfn, NEURAY_MAX_VIEWS);
-    if (a->rn < 1 || a->dn < 3 || a->dn > NEURAY_MAX_SAMPLES) return fail("neuray_render_points_backward: rn=%d dn=%d", a->rn, a->dn);
+        (det ? !rows || !keys : !a->d_ray_feats_nhwc_dev || !a->d_img_feats_nhwc_dev))
+        return fail("%s: null argument", who);
+    if (a->rfn < 1 || a->rfn > NEURAY_MAX_VIEWS) return fail("%s: rfn=%d outside [1,%d]", who, a->rfn, NEURAY_MAX_VIEWS);
+    if (a->rn < 1 || a->dn < 3 || a->dn > NEURAY_MAX_SAMPLES) return fail("%s: rn=%d dn=%d", who, a->rn, a->dn);
 #ifdef NR_INFERENCE_ONLY
-    return fail("neuray_render_points_backward: the bf16-operand library is inference only");
+    (void)stream;
+    return fail("%s: the bf16-operand library is inference only", who);
 #else
     if (a->rfn > nr::kB2Waves)
-        return fail("neuray_render_points_backward: rfn=%d - the backward covers at most %d reference views (the forward kernels take %d)",
-                    a->rfn, nr::kB2Waves, NEURAY_MAX_VIEWS);
+        return fail("%s: rfn=%d - the backward covers at most %d reference views (the forward kernels take %d)", who, a->rfn, nr::kB2Waves,
+                    NEURAY_MAX_VIEWS);
+    if (det && (long long)(a->rfn + 1) * a->fh * a->fw > 0x7fffffffLL) return fail("%s: the maps' texels do not fit a 32-bit sort key", who);
     if (!a->packed_weights_dev || !a->packed_t_weights_dev)
-        return fail("neuray_render_points_backward: packed_weights_dev and packed_t_weights_dev are needed (neuray_pack_pass_weights / neuray_pack_pass_t_index_map)");
-    if (!a->saved_dev) return fail("neuray_render_points_backward: saved_dev is NULL (run neuray_render_points with saved_dev on the same inputs first)");
-    if (!a->handover_dev) return fail("neuray_render_points_backward: handover_dev is NULL (neuray_points_backward_handover_floats(rn * dn) floats of scratch)");
+        return fail("%s: packed_weights_dev and packed_t_weights_dev are needed (neuray_pack_pass_weights / neuray_pack_pass_t_index_map)", who);
+    if (!a->saved_dev) return fail("%s: saved_dev is NULL (run neuray_render_points with saved_dev on the same inputs first)", who);
+    if (!a->handover_dev) return fail("%s: handover_dev is NULL (neuray_points_backward_handover_floats(rn * dn) floats of scratch)", who);
     nr::PointBwd2Params q;
     q.que_const = a->query_const_dev; q.view_const = a->view_const_dev; q.coords = a->coords_dev; q.depth = a->depth_dev;
     q.ray_feats = a->ray_feats_nhwc_dev; q.img_feats = a->img_feats_nhwc_dev; q.rgba = a->rgba_dev;
     q.weights = a->packed_weights_dev; q.weights_t = a->packed_t_weights_dev;
-    q.d_point_rec = a->d_point_rec_dev; q.d_flat = a->d_flat_weights_dev; q.d_ray_feats = a->d_ray_feats_nhwc_dev;
-    q.d_img_feats = a->d_img_feats_nhwc_dev; q.saved = a->saved_dev;
+    q.d_point_rec = a->d_point_rec_dev; q.saved = a->saved_dev;
+    q.d_ray_feats = det ? rows : a->d_ray_feats_nhwc_dev;
+    q.d_img_feats = det ? reinterpret_cast<float*>(keys) : a->d_img_feats_nhwc_dev;
     q.rfn = a->rfn; q.rn = a->rn; q.dn = a->dn; q.h = a->h; q.w = a->w; q.fh = a->fh; q.fw = a->fw;
     q.use_vis = a->use_vis; q.var_bias = a->var_bias;
     q.handover = a->handover_dev;
-    const int grid2 = grid_for((long long)a->rn * a->dn, 16, 256);            // persistent: one workgroup per CU
+    const int grid = points_bwd_grid(a->rn, a->dn);
     const size_t smem = nr::point_bwd2_smem_bytes();
-    auto launch = [&](auto k) {
-#ifndef NEURAY_EMU
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-        NR_LAUNCH(k, dim3(grid2), dim3(64 * nr::kB2Waves), smem, stream, q);
-    };
     // (a vis head that compute_prob does not consume - the fine decoder's when the coarse decoder has use_vis = False, quirk A.9.2 -
     // has an identically zero gradient on this path: the kernel without the head is the same computation)
     const bool vis = a->has_vis_head && a->use_vis;
-    // two launches: tail, then front (nr_kernels_bwd2.h B2Part)
-    if (vis) { launch(nr::points_backward2_kernel<true, nr::B2_TAIL>); launch(nr::points_backward2_kernel<true, nr::B2_FRONT>); }
-    else { launch(nr::points_backward2_kernel<false, nr::B2_TAIL>); launch(nr::points_backward2_kernel<false, nr::B2_FRONT>); }
-    return check_launch("neuray_render_points_backward");
+    using K = void (*)(nr::PointBwd2Params);
+    const K tail = det ? (vis ? K(nr::points_backward2_kernel<true, nr::B2_TAIL, true>) : K(nr::points_backward2_kernel<false, nr::B2_TAIL, true>))
+                       : (vis ? K(nr::points_backward2_kernel<true, nr::B2_TAIL>) : K(nr::points_backward2_kernel<false, nr::B2_TAIL>));
+    const K front = det ? (vis ? K(nr::points_backward2_kernel<true, nr::B2_FRONT, true>) : K(nr::points_backward2_kernel<false, nr::B2_FRONT, true>))
+                        : (vis ? K(nr::points_backward2_kernel<true, nr::B2_FRONT>) : K(nr::points_backward2_kernel<false, nr::B2_FRONT>));
+    // two launches: tail, then front (nr_kernels_bwd2.h B2Part), with a half of the partials each
+    float* const p_tail = partials;
+    float* const p_front = det ? partials + (size_t)grid * nr::kFlatPassFloats : nullptr;
+    q.d_flat = det ? p_tail : a->d_flat_weights_dev;
+    launch_lds(tail, dim3(grid), dim3(64 * nr::kB2Waves), smem, stream, q, true);
+    q.d_flat = det ? p_front : a->d_flat_weights_dev;
+    launch_lds(front, dim3(grid), dim3(64 * nr::kB2Waves), smem, stream, q, true);
+    if (int rc = check_launch(who)) return rc;
+    if (!det) return 0;
+    // each half has its own reduce launch, in stream order: tail's rows first, then front's
+    if (int rc = reduce_partials(who, p_tail, grid, nr::kFlatPassFloats, a->d_flat_weights_dev, stream)) return rc;
+    return reduce_partials(who, p_front, grid, nr::kFlatPassFloats, a->d_flat_weights_dev, stream);
 #endif
+}
+
+int self_hit_backward(const char* who, const float* qc, const float* depth, const float* feats, const float* packed, const float* packed_t,
+                      int has_vis_head, int use_vis, float var_bias, const float* d_hit, int rn, int dn, float* d_feats, float* d_flat,
+                      float* partials, void* stream) {
+#ifdef NR_INFERENCE_ONLY
+    return fail("%s: the bf16-operand variant is inference only", who);
+#else
+    if (!qc || !depth || !feats || !packed || !packed_t || !d_hit || !d_feats || !d_flat) return fail("%s: null argument", who);
+    if (rn < 1 || dn < 3 || dn > NEURAY_MAX_SAMPLES) return fail("%s: rn=%d dn=%d", who, rn, dn);
+    const bool det = partials != nullptr, vis = has_vis_head && use_vis;          // (an unused vis head: zero gradient)
+    nr::SelfHitBwd2Params p;
+    p.que_const = qc; p.depth = depth; p.feats = feats; p.weights = packed; p.weights_t = packed_t; p.d_hit = d_hit;
+    p.d_feats = d_feats; p.d_flat = det ? partials : d_flat; p.rn = rn; p.dn = dn; p.use_vis = use_vis; p.var_bias = var_bias;
+    const int grid = rows_bwd_grid(rn);
+    const auto k = det ? (vis ? nr::self_hit_backward2_kernel<true, true> : nr::self_hit_backward2_kernel<false, true>)
+                       : (vis ? nr::self_hit_backward2_kernel<true, false> : nr::self_hit_backward2_kernel<false, false>);
+    NR_LAUNCH(k, dim3(grid), dim3(64), 0, stream, p);
+    if (int rc = check_launch(who)) return rc;
+    return det ? reduce_partials(who, partials, grid, nr::kFlatPassFloats, d_flat, stream) : 0;
+#endif
+}
+
+int rows_backward(const char* who, const float* feats, const float* packed, const float* packed_t, int n, int has_vis_head, float var_bias,
+                  const float* d_mean, const float* d_var, const float* d_aw, const float* d_vis, float* d_feats, float* d_flat,
+                  float* partials, void* stream) {
+#ifdef NR_INFERENCE_ONLY
+    return fail("%s: the bf16-operand variant is inference only", who);
+#else
+    if (!feats || !packed || !packed_t || !d_feats || !d_flat) return fail("%s: null argument", who);
+    if (n < 1) return fail("%s: n=%d", who, n);
+    const bool det = partials != nullptr, vis = has_vis_head && d_vis;            // (no gradient into the vis head: not run)
+    nr::RowsBwd2Params p;
+    p.feats = feats; p.weights = packed; p.weights_t = packed_t; p.d_mean = d_mean; p.d_var = d_var; p.d_aw = d_aw; p.d_vis = d_vis;
+    p.d_feats = d_feats; p.d_flat = det ? partials : d_flat; p.n = n; p.var_bias = var_bias;
+    // (a persistent grid: every workgroup ends with one atomicAdd per weight of the heads it ran - 2048 of them cost more in the flush than in the rows)
+    const int grid = rows_bwd_grid(n);
+    const auto k = det ? (vis ? nr::decoder_rows_backward2_kernel<true, true> : nr::decoder_rows_backward2_kernel<false, true>)
+                       : (vis ? nr::decoder_rows_backward2_kernel<true, false> : nr::decoder_rows_backward2_kernel<false, false>);
+    NR_LAUNCH(k, dim3(grid), dim3(64), 0, stream, p);
+    if (int rc = check_launch(who)) return rc;
+    return det ? reduce_partials(who, partials, grid, nr::kFlatPassFloats, d_flat, stream) : 0;
+#endif
+}
+}  // namespace
+
+int neuray_render_points_backward(const NeurayPointsBwdArgs* a, void* stream) {
+    return points_backward("neuray_render_points_backward", a, nullptr, nullptr, nullptr, stream);
+}
+
+int neuray_render_points_backward_det(const NeurayPointsBwdArgs* a, float* partials_zeroed_dev, float* rows_dev, int* keys_dev, void* stream) {
+    if (!partials_zeroed_dev) return fail("neuray_render_points_backward_det: null argument");
+    return points_backward("neuray_render_points_backward_det", a, partials_zeroed_dev, rows_dev, keys_dev, stream);
 }
 
 int neuray_self_hit_prob_backward(const float* qc, const float* depth, const float* feats, const float* packed, const float* packed_t,
-                                           int has_vis_head, int use_vis, float var_bias, const float* d_hit, int rn, int dn,
-                                           float* d_feats, float* d_flat, void* stream) {
-#ifdef NR_INFERENCE_ONLY
-    return fail("neuray_self_hit_prob_backward: the bf16-operand variant is inference only");
-#else
-    if (!qc || !depth || !feats || !packed || !packed_t || !d_hit || !d_feats || !d_flat)
-        return fail("neuray_self_hit_prob_backward: null argument");
-    if (rn < 1 || dn < 3 || dn > NEURAY_MAX_SAMPLES) return fail("neuray_self_hit_prob_backward: rn=%d dn=%d", rn, dn);
-    nr::SelfHitBwd2Params p;
-    p.que_const = qc; p.depth = depth; p.feats = feats; p.weights = packed; p.weights_t = packed_t; p.d_hit = d_hit;
-    p.d_feats = d_feats; p.d_flat = d_flat; p.rn = rn; p.dn = dn; p.use_vis = use_vis; p.var_bias = var_bias;
-    const dim3 grid(grid_for(rn, 16, 512));
-    if (has_vis_head && use_vis) NR_LAUNCH(nr::self_hit_backward2_kernel<true>, grid, dim3(64), 0, stream, p);   // (an unused vis head: zero gradient)
-    else NR_LAUNCH(nr::self_hit_backward2_kernel<false>, grid, dim3(64), 0, stream, p);
-    return check_launch("neuray_self_hit_prob_backward");
-#endif
+                                  int has_vis_head, int use_vis, float var_bias, const float* d_hit, int rn, int dn,
+                                  float* d_feats, float* d_flat, void* stream) {
+    return self_hit_backward("neuray_self_hit_prob_backward", qc, depth, feats, packed, packed_t, has_vis_head, use_vis, var_bias, d_hit, rn, dn,
+                             d_feats, d_flat, nullptr, stream);
+}
+
+int neuray_self_hit_prob_backward_det(const float* qc, const float* depth, const float* feats, const float* packed, const float* packed_t,
+                                      int has_vis_head, int use_vis, float var_bias, const float* d_hit, int rn, int dn,
+                                      float* d_feats, float* d_flat, float* partials_zeroed_dev, void* stream) {
+    if (!partials_zeroed_dev) return fail("neuray_self_hit_prob_backward_det: null argument");
+    return self_hit_backward("neuray_self_hit_prob_backward_det", qc, depth, feats, packed, packed_t, has_vis_head, use_vis, var_bias, d_hit, rn,
+                             dn, d_feats, d_flat, partials_zeroed_dev, stream);
 }
 
 int neuray_dist_decoder_rows_backward(const float* feats, const float* packed, const float* packed_t, int n, int has_vis_head,
-                                               float var_bias, const float* d_mean, const float* d_var, const float* d_aw, const float* d_vis,
-                                               float* d_feats, float* d_flat, void* stream) {
-#ifdef NR_INFERENCE_ONLY
-    return fail("neuray_dist_decoder_rows_backward: the bf16-operand variant is inference only");
-#else
-    if (!feats || !packed || !packed_t || !d_feats || !d_flat) return fail("neuray_dist_decoder_rows_backward: null argument");
-    if (n < 1) return fail("neuray_dist_decoder_rows_backward: n=%d", n);
-    nr::RowsBwd2Params p;
-    p.feats = feats; p.weights = packed; p.weights_t = packed_t; p.d_mean = d_mean; p.d_var = d_var; p.d_aw = d_aw; p.d_vis = d_vis;
-    p.d_feats = d_feats; p.d_flat = d_flat; p.n = n; p.var_bias = var_bias;
-    // (a persistent grid: every workgroup ends with one atomicAdd per weight of the heads it ran - 2048 of them cost more in the flush than in the rows)
-    const dim3 grid(grid_for(n, 16, 512));
-    if (has_vis_head && d_vis) NR_LAUNCH(nr::decoder_rows_backward2_kernel<true>, grid, dim3(64), 0, stream, p);      // (no gradient into the vis head: not run)
-    else NR_LAUNCH(nr::decoder_rows_backward2_kernel<false>, grid, dim3(64), 0, stream, p);
-    return check_launch("neuray_dist_decoder_rows_backward");
-#endif
+                                      float var_bias, const float* d_mean, const float* d_var, const float* d_aw, const float* d_vis,
+                                      float* d_feats, float* d_flat, void* stream) {
+    return rows_backward("neuray_dist_decoder_rows_backward", feats, packed, packed_t, n, has_vis_head, var_bias, d_mean, d_var, d_aw, d_vis,
+                         d_feats, d_flat, nullptr, stream);
+}
+
+int neuray_dist_decoder_rows_backward_det(const float* feats, const float* packed, const float* packed_t, int n, int has_vis_head,
+                                          float var_bias, const float* d_mean, const float* d_var, const float* d_aw, const float* d_vis,
+                                          float* d_feats, float* d_flat, float* partials_zeroed_dev, void* stream) {
+    if (!partials_zeroed_dev) return fail("neuray_dist_decoder_rows_backward_det: null argument");
+    return rows_backward("neuray_dist_decoder_rows_backward_det", feats, packed, packed_t, n, has_vis_head, var_bias, d_mean, d_var, d_aw, d_vis,
+                         d_feats, d_flat, partials_zeroed_dev, stream);
 }
 
 int neuray_interpolate_feats_backward(const float* d_out, const float* points, const float* mask, int b, int n, int c, int fh,
@@ -948,14 +1073,9 @@ int neuray_interpolate_feats_backward_staged(const float* d_out, const float* po
     return check_launch("neuray_interpolate_feats_backward_staged");
 }
 
-// ---- the deterministic training backward (cfg['hip_deterministic']): the same kernels instantiated with DET = true - plain
-// stores of every workgroup's sums to a partials buffer - and the ordered reductions of nr_kernels_bwd.h.  No float atomics on this path.
+// ---- the rest of the deterministic training backward (the *_det entries stand next to their namesakes above): the sizes
+// of the scratch, the ordered reduction on its own, and the maps' gradients as a segmented sum over sorted keys
 namespace {
-int rays_bwd_grid(int rn, int dn) { return grid_for(rn, nr::ray_bwd_waves(dn), 256 * 4); }
-int reduce_partials(const float* partials, int g, long long n, float* out, void* stream) {
-    NR_LAUNCH(nr::reduce_partials_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, partials, g, n, out);
-    return check_launch("neuray_reduce_partials");
-}
 int scatter_sorted(const nr::ScatterSortedParams& p, void* stream) {
     NR_LAUNCH(nr::scatter_sorted_kernel, dim3(grid_for(p.ntex, 4, 256 * 16)), dim3(256), 0, stream, p);
     return check_launch("scatter_sorted");
@@ -967,8 +1087,8 @@ size_t neuray_deterministic_partials_floats(int kernel, int rn, int dn) {
     switch (kernel) {
         case NEURAY_DET_RAYS: return dn < 1 ? 0 : (size_t)rays_bwd_grid(rn, dn) * nr::kPackedRayFloats;
 #ifndef NR_INFERENCE_ONLY
-        case NEURAY_DET_POINTS: return dn < 1 ? 0 : (size_t)2 * grid_for((long long)rn * dn, 16, 256) * nr::kFlatPassFloats;
-        case NEURAY_DET_SELF_HIT: case NEURAY_DET_ROWS: return (size_t)grid_for(rn, 16, 512) * nr::kFlatPassFloats;
+        case NEURAY_DET_POINTS: return dn < 1 ? 0 : (size_t)2 * points_bwd_grid(rn, dn) * nr::kFlatPassFloats;       // (tail's rows, then front's)
+        case NEURAY_DET_SELF_HIT: case NEURAY_DET_ROWS: return (size_t)rows_bwd_grid(rn) * nr::kFlatPassFloats;
 #endif
         default: return 0;
     }
@@ -977,37 +1097,7 @@ size_t neuray_deterministic_partials_floats(int kernel, int rn, int dn) {
 int neuray_reduce_partials(const float* partials_dev, int g, long long n, float* out_dev, void* stream) {
     if (!partials_dev || !out_dev) return fail("neuray_reduce_partials: null argument");
     if (g < 1 || n < 1) return fail("neuray_reduce_partials: g=%d n=%lld", g, n);
-    return reduce_partials(partials_dev, g, n, out_dev, stream);
-}
-
-int neuray_render_rays_backward_det(const NeurayRaysBwdArgs* a, float* partials_dev, void* stream) {
-    if (!a || !a->point_rec_dev || !a->depth_dev || !a->pos_enc_dev || !a->packed_weights_dev || !a->d_pixel_dev ||
-        !a->d_point_rec_dev || !a->d_ray_weights_dev || !partials_dev)
-        return fail("neuray_render_rays_backward_det: null argument");
-    if (a->rn < 1) return fail("neuray_render_rays_backward_det: rn=%d", a->rn);
-    if (a->dn < 3 || a->dn > NEURAY_MAX_SAMPLES) return fail("neuray_render_rays_backward_det: dn=%d outside [3,%d]", a->dn, NEURAY_MAX_SAMPLES);
-    nr::RayBwdParams p;
-    p.point_rec = a->point_rec_dev; p.depth = a->depth_dev; p.pos_enc = a->pos_enc_dev; p.weights = a->packed_weights_dev;
-    p.d_pixel = a->d_pixel_dev; p.d_hit_prob = a->d_hit_prob_dev; p.d_depth = a->d_render_depth_dev;
-    p.d_point_rec = a->d_point_rec_dev; p.d_weights = partials_dev; p.att_saved = a->att_saved_dev; p.rn = a->rn; p.dn = a->dn;
-    const size_t smem = nr::ray_bwd_smem_bytes(a->dn, true);
-    const int waves = nr::ray_bwd_waves(a->dn);
-    const int grid = rays_bwd_grid(a->rn, a->dn);
-    if (a->dn <= 64) {
-        auto k = nr::rays_backward_kernel<1, true>;
-#ifndef NEURAY_EMU
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-        NR_LAUNCH(k, dim3(grid), dim3(64 * waves), smem, stream, p);
-    } else {
-        auto k = nr::rays_backward_kernel<2, true>;
-#ifndef NEURAY_EMU
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-        NR_LAUNCH(k, dim3(grid), dim3(64 * waves), smem, stream, p);
-    }
-    if (int rc = check_launch("neuray_render_rays_backward_det")) return rc;
-    return reduce_partials(partials_dev, grid, nr::kPackedRayFloats, a->d_ray_weights_dev, stream);
+    return reduce_partials("neuray_reduce_partials", partials_dev, g, n, out_dev, stream);
 }
 
 long long neuray_points_backward_scatter_columns(int npoints) {
@@ -1016,51 +1106,6 @@ long long neuray_points_backward_scatter_columns(int npoints) {
     return 0;
 #else
     return npoints < 1 ? 0 : (long long)((npoints + 15) / 16) * 16 * nr::kB2Waves;
-#endif
-}
-
-int neuray_render_points_backward_det(const NeurayPointsBwdArgs* a, float* partials_zeroed_dev, float* rows_dev, int* keys_dev, void* stream) {
-    if (!a || !a->query_const_dev || !a->view_const_dev || !a->coords_dev || !a->depth_dev || !a->ray_feats_nhwc_dev ||
-        !a->img_feats_nhwc_dev || !a->rgba_dev || !a->flat_weights_dev || !a->d_point_rec_dev || !a->d_flat_weights_dev ||
-        !partials_zeroed_dev || !rows_dev || !keys_dev)
-        return fail("neuray_render_points_backward_det: null argument");
-    if (a->rfn < 1 || a->rfn > NEURAY_MAX_VIEWS) return fail("neuray_render_points_backward_det: rfn=%d outside [1,%d]", a->rfn, NEURAY_MAX_VIEWS);
-    if (a->rn < 1 || a->dn < 3 || a->dn > NEURAY_MAX_SAMPLES) return fail("neuray_render_points_backward_det: rn=%d dn=%d", a->rn, a->dn);
-#ifdef NR_INFERENCE_ONLY
-    return fail("neuray_render_points_backward_det: the bf16-operand library is inference only");
-#else
-    if (a->rfn > nr::kB2Waves)
-        return fail("neuray_render_points_backward_det: rfn=%d - the backward covers at most %d reference views", a->rfn, nr::kB2Waves);
-    if ((long long)(a->rfn + 1) * a->fh * a->fw > 0x7fffffffLL) return fail("neuray_render_points_backward_det: the maps' texels do not fit a 32-bit sort key");
-    if (!a->packed_weights_dev || !a->packed_t_weights_dev || !a->saved_dev || !a->handover_dev)
-        return fail("neuray_render_points_backward_det: packed_weights_dev, packed_t_weights_dev, saved_dev and handover_dev are needed (as neuray_render_points_backward)");
-    nr::PointBwd2Params q;
-    q.que_const = a->query_const_dev; q.view_const = a->view_const_dev; q.coords = a->coords_dev; q.depth = a->depth_dev;
-    q.ray_feats = a->ray_feats_nhwc_dev; q.img_feats = a->img_feats_nhwc_dev; q.rgba = a->rgba_dev;
-    q.weights = a->packed_weights_dev; q.weights_t = a->packed_t_weights_dev;
-    q.d_point_rec = a->d_point_rec_dev; q.saved = a->saved_dev;
-    q.d_ray_feats = rows_dev; q.d_img_feats = reinterpret_cast<float*>(keys_dev);       // (the DET instantiation's meaning of the two fields)
-    q.rfn = a->rfn; q.rn = a->rn; q.dn = a->dn; q.h = a->h; q.w = a->w; q.fh = a->fh; q.fw = a->fw;
-    q.use_vis = a->use_vis; q.var_bias = a->var_bias;
-    q.handover = a->handover_dev;
-    const int grid2 = grid_for((long long)a->rn * a->dn, 16, 256);
-    const size_t smem = nr::point_bwd2_smem_bytes();
-    auto launch = [&](auto k, float* partials) {
-        q.d_flat = partials;
-#ifndef NEURAY_EMU
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-        NR_LAUNCH(k, dim3(grid2), dim3(64 * nr::kB2Waves), smem, stream, q);
-    };
-    float* p_tail = partials_zeroed_dev;
-    float* p_front = partials_zeroed_dev + (size_t)grid2 * nr::kFlatPassFloats;
-    const bool vis = a->has_vis_head && a->use_vis;
-    if (vis) { launch(nr::points_backward2_kernel<true, nr::B2_TAIL, true>, p_tail); launch(nr::points_backward2_kernel<true, nr::B2_FRONT, true>, p_front); }
-    else { launch(nr::points_backward2_kernel<false, nr::B2_TAIL, true>, p_tail); launch(nr::points_backward2_kernel<false, nr::B2_FRONT, true>, p_front); }
-    if (int rc = check_launch("neuray_render_points_backward_det")) return rc;
-    // each half has its own reduce launch, in stream order: tail's rows first, then front's
-    if (int rc = reduce_partials(p_tail, grid2, nr::kFlatPassFloats, a->d_flat_weights_dev, stream)) return rc;
-    return reduce_partials(p_front, grid2, nr::kFlatPassFloats, a->d_flat_weights_dev, stream);
 #endif
 }
 
@@ -1078,45 +1123,6 @@ int neuray_points_backward_scatter(const int* sorted_keys_dev, const long long* 
     p.m = columns * 4; p.img_stride = (long long)fh * fw * 32; p.tex_stride = 32; p.ch_stride = 1;
     p.ntex = rfn * fh * fw; p.hw = fh * fw; p.c = 64; p.split = 32; p.g_stride = nr::kB2ScatterRow; p.w_stride = nr::kB2ScatterRow;
     return scatter_sorted(p, stream);
-#endif
-}
-
-int neuray_self_hit_prob_backward_det(const float* qc, const float* depth, const float* feats, const float* packed, const float* packed_t,
-                                      int has_vis_head, int use_vis, float var_bias, const float* d_hit, int rn, int dn,
-                                      float* d_feats, float* d_flat, float* partials_zeroed_dev, void* stream) {
-#ifdef NR_INFERENCE_ONLY
-    return fail("neuray_self_hit_prob_backward_det: the bf16-operand variant is inference only");
-#else
-    if (!qc || !depth || !feats || !packed || !packed_t || !d_hit || !d_feats || !d_flat || !partials_zeroed_dev)
-        return fail("neuray_self_hit_prob_backward_det: null argument");
-    if (rn < 1 || dn < 3 || dn > NEURAY_MAX_SAMPLES) return fail("neuray_self_hit_prob_backward_det: rn=%d dn=%d", rn, dn);
-    nr::SelfHitBwd2Params p;
-    p.que_const = qc; p.depth = depth; p.feats = feats; p.weights = packed; p.weights_t = packed_t; p.d_hit = d_hit;
-    p.d_feats = d_feats; p.d_flat = partials_zeroed_dev; p.rn = rn; p.dn = dn; p.use_vis = use_vis; p.var_bias = var_bias;
-    const int g = grid_for(rn, 16, 512);
-    if (has_vis_head && use_vis) { auto k = nr::self_hit_backward2_kernel<true, true>; NR_LAUNCH(k, dim3(g), dim3(64), 0, stream, p); }
-    else { auto k = nr::self_hit_backward2_kernel<false, true>; NR_LAUNCH(k, dim3(g), dim3(64), 0, stream, p); }
-    if (int rc = check_launch("neuray_self_hit_prob_backward_det")) return rc;
-    return reduce_partials(partials_zeroed_dev, g, nr::kFlatPassFloats, d_flat, stream);
-#endif
-}
-
-int neuray_dist_decoder_rows_backward_det(const float* feats, const float* packed, const float* packed_t, int n, int has_vis_head,
-                                          float var_bias, const float* d_mean, const float* d_var, const float* d_aw, const float* d_vis,
-                                          float* d_feats, float* d_flat, float* partials_zeroed_dev, void* stream) {
-#ifdef NR_INFERENCE_ONLY
-    return fail("neuray_dist_decoder_rows_backward_det: the bf16-operand variant is inference only");
-#else
-    if (!feats || !packed || !packed_t || !d_feats || !d_flat || !partials_zeroed_dev) return fail("neuray_dist_decoder_rows_backward_det: null argument");
-    if (n < 1) return fail("neuray_dist_decoder_rows_backward_det: n=%d", n);
-    nr::RowsBwd2Params p;
-    p.feats = feats; p.weights = packed; p.weights_t = packed_t; p.d_mean = d_mean; p.d_var = d_var; p.d_aw = d_aw; p.d_vis = d_vis;
-    p.d_feats = d_feats; p.d_flat = partials_zeroed_dev; p.n = n; p.var_bias = var_bias;
-    const int g = grid_for(n, 16, 512);
-    if (has_vis_head && d_vis) { auto k = nr::decoder_rows_backward2_kernel<true, true>; NR_LAUNCH(k, dim3(g), dim3(64), 0, stream, p); }
-    else { auto k = nr::decoder_rows_backward2_kernel<false, true>; NR_LAUNCH(k, dim3(g), dim3(64), 0, stream, p); }
-    if (int rc = check_launch("neuray_dist_decoder_rows_backward_det")) return rc;
-    return reduce_partials(partials_zeroed_dev, g, nr::kFlatPassFloats, d_flat, stream);
 #endif
 }
 
@@ -1143,47 +1149,6 @@ int neuray_interpolate_feats_backward_sorted(const float* d_out, const float* ma
 int neuray_inorm_chunks(int n, int c, int h, int w) {
     if (n < 1 || c < 1 || h < 1 || w < 1) return 0;
     return norm_chunks(n * c, h * w);
-}
-
-int neuray_inorm_forward_det(const float* x, const float* gamma, const float* beta, const float* res, long long res_stride_n,
-                             long long res_stride_c, long long res_stride_h, int n, int c, int h, int w, int pad, int act, float eps,
-                             float* partials, float* raw, float* stats, float* out_padded, long long out_stride_n, void* stream) {
-    if (!x || !gamma || !beta || !partials || !raw || !stats || !out_padded) return fail("neuray_inorm_forward_det: null pointer");
-    if (n < 1 || c < 1 || h < 1 || w < 1 || pad < 0 || pad >= h || pad >= w || act < 0 || act > 2 || (long long)(h + 2 * pad) * (w + 2 * pad) >= (1 << 23))
-        return fail("neuray_inorm_forward_det: bad arguments n=%d c=%d h=%d w=%d pad=%d act=%d", n, c, h, w, pad, act);
-    const long long img = (long long)c * (h + 2 * pad) * (w + 2 * pad);
-    if (out_stride_n != 0 && out_stride_n < img) return fail("neuray_inorm_forward_det: out_stride_n %lld < %lld", out_stride_n, img);
-    const int planes = n * c, hw = h * w, chunks = norm_chunks(planes, hw);
-    NR_LAUNCH(nr::inorm_stats_kernel<true>, dim3(chunks, planes), dim3(256), 0, stream, x, hw, partials);
-    NR_LAUNCH(nr::inorm_finish_kernel, dim3((2 * planes + 255) / 256), dim3(256), 0, stream, (const float*)partials, planes, chunks, raw);
-    nr::NormApplyParams p;
-    p.x = x; p.raw = raw; p.gamma = gamma; p.beta = beta; p.res = res; p.out = out_padded; p.stats = stats;
-    p.rs_n = res_stride_n; p.rs_c = res_stride_c; p.rs_h = res_stride_h; p.out_stride_n = out_stride_n ? out_stride_n : img;
-    p.n = n; p.c = c; p.h = h; p.w = w; p.pad = pad; p.act = act; p.eps = eps;
-    NR_LAUNCH(nr::inorm_apply_kernel, dim3(norm_chunks(planes, (h + 2 * pad) * (w + 2 * pad)), planes), dim3(256), 0, stream, p);
-    return check_launch("neuray_inorm_forward_det");
-}
-
-int neuray_inorm_backward_det(const float* x, const float* out_padded, long long out_stride_n, const float* d_out_padded, long long d_out_stride_n,
-                              const float* stats, const float* gamma, int n, int c, int h, int w, int pad, int act, float* partials, float* raw,
-                              float* dx, float* d_res, float* d_gamma, float* d_beta, void* stream) {
-    if (!x || !out_padded || !d_out_padded || !stats || !gamma || !partials || !raw || !dx) return fail("neuray_inorm_backward_det: null pointer");
-    if (n < 1 || c < 1 || h < 1 || w < 1 || pad < 0 || pad >= h || pad >= w || act < 0 || act > 2 || (long long)(h + 2 * pad) * (w + 2 * pad) >= (1 << 23))
-        return fail("neuray_inorm_backward_det: bad arguments n=%d c=%d h=%d w=%d pad=%d act=%d", n, c, h, w, pad, act);
-    const long long img = (long long)c * (h + 2 * pad) * (w + 2 * pad);
-    if ((out_stride_n != 0 && out_stride_n < img) || (d_out_stride_n != 0 && d_out_stride_n < img))
-        return fail("neuray_inorm_backward_det: image strides %lld / %lld < %lld", out_stride_n, d_out_stride_n, img);
-    nr::NormBwdParams p;
-    p.x = x; p.out = out_padded; p.d_out = d_out_padded; p.stats = stats; p.gamma = gamma; p.raw = partials; p.dx = dx; p.d_res = d_res;
-    p.d_gamma = d_gamma; p.d_beta = d_beta;
-    p.out_stride_n = out_stride_n ? out_stride_n : img; p.d_out_stride_n = d_out_stride_n ? d_out_stride_n : img;
-    p.n = n; p.c = c; p.h = h; p.w = w; p.pad = pad; p.act = act;
-    const int planes = n * c, hw = h * w, chunks = norm_chunks(planes, hw);
-    NR_LAUNCH(nr::inorm_backward_reduce_kernel<true>, dim3(chunks, planes), dim3(256), 0, stream, p);
-    NR_LAUNCH(nr::inorm_finish_kernel, dim3((2 * planes + 255) / 256), dim3(256), 0, stream, (const float*)partials, planes, chunks, raw);
-    p.raw = raw;
-    NR_LAUNCH(nr::inorm_backward_apply_kernel, dim3(chunks, planes), dim3(256), 0, stream, p);
-    return check_launch("neuray_inorm_backward_det");
 }
 
 int neuray_group_sum_selftest(const float* x, float* y, void* stream) {
@@ -1236,10 +1201,7 @@ int neuray_image_metrics(const NeurayImageMetricsArgs* a, void* stream) {
     const bool gauss = a->variant == NEURAY_SSIM_GAUSS11;
     auto k = gauss ? nr::image_metrics_tile_kernel<true> : nr::image_metrics_tile_kernel<false>;
     const size_t smem = gauss ? nr::metrics_smem_bytes<true>() : nr::metrics_smem_bytes<false>();     // 86 304 / 53 024 bytes
-#ifndef NEURAY_EMU
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-#endif
-    NR_LAUNCH(k, dim3((unsigned)blocks), dim3(nr::kMetThreads), smem, stream, p);
+    launch_lds(k, dim3((unsigned)blocks), dim3(nr::kMetThreads), smem, stream, p);
     if (int rc = check_launch("neuray_image_metrics")) return rc;
     NR_LAUNCH(nr::image_metrics_reduce_kernel, dim3(p.n), dim3(64), 4 * 64 * 8, stream, p);
     return check_launch("neuray_image_metrics");
