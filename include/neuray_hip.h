@@ -699,6 +699,61 @@ typedef struct NeurayProceduralArgs {
 } NeurayProceduralArgs;
 int neuray_procedural_render(const NeurayProceduralArgs* args, void* stream);
 
+/* ---- geometry export (neuray_amd/geometry.py; added within ABI 11: everything above is unchanged).  Depth-map consistency
+ * filter and point-cloud fusion, the fp32 library only (the bf16-operand variants return an error), inference only.  Pixel centres sit at
+ * integer coordinates; depth is the z-depth of depth2points, 0 = none.  nn_ids_dev [n][n_src] int32 names the source views of every view; -1
+ * or the view itself marks an unused slot; 1 <= n_src <= NEURAY_FUSE_MAX_SRC.  For pixel (x, y) of view i with d > 0 and slot s, j =
+ * nn_ids[i][s]: Xw = R_i^T (K_i^-1 [x,y,1]^T d - t_i); Pc = R_j Xw + t_j, z = Pc.z, (u, v) = (K_j Pc).xy / (K_j Pc).z, (un, vn) =
+ * floor((u, v) + 0.5) - the NEAREST texel, never an interpolated depth; seen: z > 0, the texel inside the image, d_j = D_j[vn][un] > 0;
+ * Yw = R_j^T (K_j^-1 [un,vn,1]^T d_j - t_j), Qc = R_i Yw + t_i, q' = K_i Qc; e_px^2 = (q'.x / q'.z - x)^2 + (q'.y / q'.z - y)^2, e_d =
+ * |Qc.z - d| / d; consistent: seen, Qc.z > 0, e_px^2 < tau_px^2, e_d < tau_d; occluded: seen, not consistent, (z - d_j) / d_j > tau_d.
+ * neuray_depth_consistency (all views, one launch) writes, each unless NULL: count [n][h][w] (consistent slots), fused_depth [n][h][w] =
+ * (d + sum of Qc.z over the consistent slots in slot order) / (1 + count), 0 where d = 0; consistent_bits / occluded_bits [n][h][w] (bit s =
+ * slot s); src_texel [n][n_src][h][w] = vn * w + un where seen, else -1.
+ * neuray_fuse_view (one view per call; call the views in ascending order on one stream) reads those outputs: a pixel is kept where count >=
+ * min_views and emitted where kept and taken[view][pixel] == 0; an emitted pixel stores 1 into taken[j][texel] of every consistent source
+ * (taken_dev [n][h][w], zeroed once by the caller; dedup = 0 skips this).  Outputs of the view: emit [h][w]; xyz [h][w][3] = the world point
+ * of the fused depth; colour [h][w][3] = the mean of the pixel's colour and the consistent source texels' colours (rgb_dev [n][3][h][w]);
+ * normal [h][w][3] = the unit cross product of the x and y differences of the camera-space points of fused_depth (central where both
+ * neighbours are kept and within tau_n * fused_depth, one-sided where one is, zero otherwise), facing the camera, in world space.  Pixels that
+ * are not emitted hold zeros.  colour_dev and normal_dev may be NULL. */
+#define NEURAY_FUSE_MAX_SRC 16
+typedef struct NeurayDepthConsistencyArgs {
+    const float* depth_dev;            /* [n][h][w] */
+    const float* poses_dev;            /* [n][3][4] world -> camera */
+    const float* Ks_dev;               /* [n][3][3] */
+    const float* Ks_inv_dev;           /* [n][3][3] */
+    const int* nn_ids_dev;             /* [n][n_src] */
+    unsigned char* count_dev;
+    float* fused_depth_dev;
+    unsigned* consistent_bits_dev;
+    unsigned* occluded_bits_dev;
+    int* src_texel_dev;
+    int n, h, w, n_src;
+    float tau_px, tau_d;
+} NeurayDepthConsistencyArgs;
+int neuray_depth_consistency(const NeurayDepthConsistencyArgs* args, void* stream);
+
+typedef struct NeurayFuseViewArgs {
+    const float* depth_dev;
+    const float* poses_dev;
+    const float* Ks_dev;
+    const float* Ks_inv_dev;
+    const int* nn_ids_dev;
+    const unsigned char* count_dev;    /* the three outputs of neuray_depth_consistency */
+    const float* fused_depth_dev;
+    const unsigned* consistent_bits_dev;
+    const float* rgb_dev;              /* [n][3][h][w] */
+    unsigned char* taken_dev;          /* [n][h][w] */
+    unsigned char* emit_dev;
+    float* xyz_dev;
+    float* colour_dev;
+    float* normal_dev;
+    int n, h, w, n_src, view, min_views, dedup, reserved;
+    float tau_n, reserved_f;
+} NeurayFuseViewArgs;
+int neuray_fuse_view(const NeurayFuseViewArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,19 @@ class NeurayProceduralArgs(C.Structure):
         [(n, C.c_int) for n in ('n_prims', 'n', 'h', 'w', 'ss', 'reserved')]
 
 
+class NeurayDepthConsistencyArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('depth_dev', 'poses_dev', 'Ks_dev', 'Ks_inv_dev', 'nn_ids_dev', 'count_dev', 'fused_depth_dev',
+                                          'consistent_bits_dev', 'occluded_bits_dev', 'src_texel_dev')] + \
+        [(n, C.c_int) for n in ('n', 'h', 'w', 'n_src')] + [('tau_px', C.c_float), ('tau_d', C.c_float)]
+
+
+class NeurayFuseViewArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('depth_dev', 'poses_dev', 'Ks_dev', 'Ks_inv_dev', 'nn_ids_dev', 'count_dev', 'fused_depth_dev',
+                                          'consistent_bits_dev', 'rgb_dev', 'taken_dev', 'emit_dev', 'xyz_dev', 'colour_dev', 'normal_dev')] + \
+        [(n, C.c_int) for n in ('n', 'h', 'w', 'n_src', 'view', 'min_views', 'dedup', 'reserved')] + [('tau_n', C.c_float), ('reserved_f', C.c_float)]
+
+
+FUSE_MAX_SRC = 16              # include/neuray_hip.h NEURAY_FUSE_MAX_SRC
 PROC_HEADER, PROC_PRIM, PROC_MAX_PRIMS = 16, 48, 32   # the scene array of neuray_procedural_render (include/neuray_hip.h NEURAY_PROC_*)
 LOSS_RENDER, LOSS_CONSIST, LOSS_DEPTH = 0, 1, 2   # NeurayLossTerm.kind (include/neuray_hip.h NEURAY_LOSS_*)
 LOSS_MAX_TERMS = 4
@@ -237,6 +250,9 @@ SYMBOLS = {
     'neuray_inorm_forward_det': (C.c_int, [C.c_void_p] * 4 + [C.c_longlong] * 3 + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 4 + [C.c_longlong, C.c_void_p]),
     # procedural scenes
     'neuray_procedural_render': (C.c_int, [C.POINTER(NeurayProceduralArgs), C.c_void_p]),
+    # geometry export
+    'neuray_depth_consistency': (C.c_int, [C.POINTER(NeurayDepthConsistencyArgs), C.c_void_p]),
+    'neuray_fuse_view': (C.c_int, [C.POINTER(NeurayFuseViewArgs), C.c_void_p]),
     'neuray_inorm_backward_det': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 7),
 }
 

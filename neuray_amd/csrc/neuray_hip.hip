@@ -20,6 +20,7 @@
 #include "nr_kernels_dr.h"          // (after the NR_INFERENCE_ONLY decision: its backward half is training only)
 #ifndef NR_BF16_QUADS
 #include "nr_kernels_vis.h"         // (fp32 MFMA only: the bf16-operand builds leave the visibility entries returning an error)
+#include "nr_kernels_fuse.h"        // (the fp32 library only, like the visibility entries)
 #endif
 #include "nr_pack.h"
 #include "../../include/neuray_hip.h"
@@ -79,6 +80,9 @@ static_assert(NEURAY_PASS_TENSORS == nr::T_COUNT, "abi");
 static_assert(NEURAY_DBG_FIELDS == nr::kDbgFields, "abi");
 static_assert(NEURAY_RAY_ATT_SAVE == nr::kRayAttSave, "abi");
 static_assert(NEURAY_MAX_SAMPLES == nr::kMaxSamples, "abi");
+#ifndef NR_BF16_QUADS
+static_assert(NEURAY_FUSE_MAX_SRC == nr::kFuseMaxSrc, "abi");
+#endif
 static_assert(NEURAY_PROC_HEADER == nr::kProcHeader && NEURAY_PROC_PRIM == nr::kProcPrim && NEURAY_PROC_MAX_PRIMS == nr::kProcMaxPrims, "abi");
 
 template <int NT, int VPW, bool HAS_VIS, int OWN, int MINW, bool SAVE = false, int AR = nr::AR_F32>
@@ -1390,6 +1394,64 @@ int neuray_procedural_render(const NeurayProceduralArgs* a, void* stream) {
     const dim3 grid((unsigned)((a->w + nr::kProcTileX - 1) / nr::kProcTileX), (unsigned)((a->h + nr::kProcTileY - 1) / nr::kProcTileY), (unsigned)a->n);
     NR_LAUNCH(nr::procedural_render_kernel, grid, dim3(nr::kProcTileX * nr::kProcTileY), 0, stream, p);
     return check_launch("neuray_procedural_render");
+}
+
+// ---- geometry export ----
+#ifndef NR_BF16_QUADS
+static int fuse_common(const char* who, const void* depth, const void* poses, const void* Ks, const void* Ks_inv, const void* nn_ids, int n, int h,
+                       int w, int n_src) {
+    if (n < 1 || h < 1 || w < 1) return fail("%s: bad size n=%d h=%d w=%d", who, n, h, w);
+    if (n_src < 1 || n_src > NEURAY_FUSE_MAX_SRC) return fail("%s: n_src=%d outside [1,%d]", who, n_src, NEURAY_FUSE_MAX_SRC);
+    if (n > 65535 || (h + nr::kFuseTileY - 1) / nr::kFuseTileY > 65535) return fail("%s: n=%d h=%d too large for one call", who, n, h);
+    if ((long long)h * w > 0x7fffffffLL) return fail("%s: h*w too large (a texel index is an int)", who);
+    if (!depth || !poses || !Ks || !Ks_inv || !nn_ids) return fail("%s: depth / poses / Ks / Ks_inv / nn_ids missing", who);
+    return 0;
+}
+#endif
+
+int neuray_depth_consistency(const NeurayDepthConsistencyArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_depth_consistency: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_depth_consistency: null args");
+    if (int rc = fuse_common("neuray_depth_consistency", a->depth_dev, a->poses_dev, a->Ks_dev, a->Ks_inv_dev, a->nn_ids_dev, a->n, a->h, a->w, a->n_src)) return rc;
+    if (!(a->tau_px > 0.0f) || !(a->tau_d > 0.0f)) return fail("neuray_depth_consistency: thresholds must be positive (tau_px=%g tau_d=%g)", a->tau_px, a->tau_d);
+    nr::FuseConsistencyParams p;
+    p.depth = a->depth_dev; p.poses = a->poses_dev; p.Ks = a->Ks_dev; p.Ks_inv = a->Ks_inv_dev; p.nn_ids = a->nn_ids_dev;
+    p.count = a->count_dev; p.fused_depth = a->fused_depth_dev; p.consistent_bits = a->consistent_bits_dev; p.occluded_bits = a->occluded_bits_dev;
+    p.src_texel = a->src_texel_dev;
+    p.n = a->n; p.h = a->h; p.w = a->w; p.S = a->n_src; p.tau_px = a->tau_px; p.tau_d = a->tau_d;
+    const dim3 grid((unsigned)((a->w + nr::kFuseTileX - 1) / nr::kFuseTileX), (unsigned)((a->h + nr::kFuseTileY - 1) / nr::kFuseTileY), (unsigned)a->n);
+    NR_LAUNCH(nr::depth_consistency_kernel, grid, dim3(nr::kFuseTileX * nr::kFuseTileY), 0, stream, p);
+    return check_launch("neuray_depth_consistency");
+#endif
+}
+
+int neuray_fuse_view(const NeurayFuseViewArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_fuse_view: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_fuse_view: null args");
+    if (int rc = fuse_common("neuray_fuse_view", a->depth_dev, a->poses_dev, a->Ks_dev, a->Ks_inv_dev, a->nn_ids_dev, a->n, a->h, a->w, a->n_src)) return rc;
+    if (a->view < 0 || a->view >= a->n) return fail("neuray_fuse_view: view=%d outside [0,%d)", a->view, a->n);
+    if (a->min_views < 1) return fail("neuray_fuse_view: min_views=%d (at least 1)", a->min_views);
+    if (!(a->tau_n > 0.0f)) return fail("neuray_fuse_view: thresholds must be positive (tau_n=%g)", a->tau_n);
+    if (!a->count_dev || !a->fused_depth_dev || !a->consistent_bits_dev) return fail("neuray_fuse_view: count / fused_depth / consistent_bits missing");
+    if (!a->emit_dev || !a->xyz_dev) return fail("neuray_fuse_view: emit / xyz missing");
+    if (a->colour_dev && !a->rgb_dev) return fail("neuray_fuse_view: colour asked for without rgb");
+    if (a->dedup && !a->taken_dev) return fail("neuray_fuse_view: dedup set but taken missing");
+    nr::FuseParams p;
+    p.depth = a->depth_dev; p.poses = a->poses_dev; p.Ks = a->Ks_dev; p.Ks_inv = a->Ks_inv_dev; p.nn_ids = a->nn_ids_dev;
+    p.count = a->count_dev; p.fused_depth = a->fused_depth_dev; p.consistent_bits = a->consistent_bits_dev; p.rgb = a->rgb_dev;
+    p.taken = a->dedup ? a->taken_dev : nullptr;
+    p.emit = a->emit_dev; p.xyz = a->xyz_dev; p.colour = a->colour_dev; p.normal = a->normal_dev;
+    p.n = a->n; p.h = a->h; p.w = a->w; p.S = a->n_src; p.view = a->view; p.min_views = a->min_views; p.tau_n = a->tau_n;
+    const dim3 grid((unsigned)((a->w + nr::kFuseTileX - 1) / nr::kFuseTileX), (unsigned)((a->h + nr::kFuseTileY - 1) / nr::kFuseTileY), 1u);
+    NR_LAUNCH(nr::fuse_view_kernel, grid, dim3(nr::kFuseTileX * nr::kFuseTileY), 0, stream, p);
+    return check_launch("neuray_fuse_view");
+#endif
 }
 
 #ifdef NR_B2_PROFILE

@@ -996,6 +996,75 @@ class RenderEngine:
         self._event_done(ev, 'procedural', n * int(h) * int(w))
         return out
 
+    # ---- geometry export (neuray_amd/geometry.py) ----
+    def _fuse_inputs(self, depth, poses, Ks, nn_ids, Ks_inv):
+        if self.variant != 'fp32':
+            raise NotImplementedError("neuray_amd: the geometry export lives in the fp32 library (variant=%r)" % (self.variant,))
+        depth = self._f32(torch.as_tensor(depth))
+        if depth.dim() == 4:
+            depth = depth[:, 0].contiguous()
+        poses = self._f32(torch.as_tensor(poses)).reshape(-1, 3, 4)
+        n = poses.shape[0]
+        assert depth.dim() == 3 and depth.shape[0] == n, "depth [n,h,w] for %d poses: %s" % (n, tuple(depth.shape))
+        if Ks_inv is None:                         # (a device -> host copy when Ks lives on the device: hand Ks_inv over to avoid it)
+            Ks_inv = host_inverse(torch.as_tensor(Ks).reshape(-1, 3, 3))
+        Ks, Ks_inv = self._f32(torch.as_tensor(Ks)).reshape(-1, 3, 3), self._f32(torch.as_tensor(Ks_inv)).reshape(-1, 3, 3)
+        nn_ids = torch.as_tensor(nn_ids).detach().to(device=self.device, dtype=torch.int32).contiguous()
+        assert Ks.shape[0] == n and Ks_inv.shape[0] == n and nn_ids.dim() == 2 and nn_ids.shape[0] == n
+        return depth, poses, Ks, Ks_inv, nn_ids
+
+    def depth_consistency(self, depth, poses, Ks, nn_ids, tau_px=1.0, tau_d=0.01, Ks_inv=None,
+                          outputs=('count', 'fused_depth', 'consistent_bits', 'occluded_bits')):
+        """The cross-view consistency test of every pixel of every view in one launch (include/neuray_hip.h, neuray_depth_consistency).
+        depth [n,h,w] (z-depth, 0 = none), poses [n,3,4], Ks [n,3,3], nn_ids [n,S] (-1 or the view itself: an unused slot) -> dict of
+        device tensors, as named in `outputs`: count [n,h,w] uint8, fused_depth [n,h,w] float32, consistent_bits / occluded_bits
+        [n,h,w] int32 (bit s = slot s; S <= 16, so the sign bit is never set), src_texel [n,S,h,w] int32.  No host synchronisation."""
+        depth, poses, Ks, Ks_inv, nn_ids = self._fuse_inputs(depth, poses, Ks, nn_ids, Ks_inv)
+        n, h, w = depth.shape
+        S = nn_ids.shape[1]
+        kinds = {'count': ((n, h, w), torch.uint8), 'fused_depth': ((n, h, w), torch.float32), 'consistent_bits': ((n, h, w), torch.int32),
+                 'occluded_bits': ((n, h, w), torch.int32), 'src_texel': ((n, S, h, w), torch.int32)}
+        out = {k: self.empty(*kinds[k][0], dtype=kinds[k][1]) for k in kinds if k in outputs}
+        ptr = lambda k: out[k].data_ptr() if k in out else None     # noqa: E731
+        a = _lib.NeurayDepthConsistencyArgs(depth.data_ptr(), poses.data_ptr(), Ks.data_ptr(), Ks_inv.data_ptr(), nn_ids.data_ptr(), ptr('count'),
+                                            ptr('fused_depth'), ptr('consistent_bits'), ptr('occluded_bits'), ptr('src_texel'), n, h, w, S,
+                                            float(tau_px), float(tau_d))
+        ev = self._event_pair()
+        self._check(self.lib.neuray_depth_consistency(C.byref(a), self._stream()))
+        self._event_done(ev, 'depth_consistency', n * h * w)
+        return out
+
+    def fuse_view(self, view, depth, imgs, poses, Ks, nn_ids, consistency, taken=None, min_views=2, tau_n=0.05, Ks_inv=None,
+                  outputs=('colour', 'normal')):
+        """One view of the point-cloud fusion (neuray_fuse_view; the caller runs the views in ascending order on one stream).
+        consistency: depth_consistency's count, fused_depth and consistent_bits; imgs [n,3,h,w]; taken [n,h,w] uint8, zeroed once by the
+        caller and shared by the calls of one fusion (None: no de-duplication) -> dict of device tensors: emit [h,w] uint8, xyz [h,w,3]
+        and, as named in `outputs`, colour [h,w,3], normal [h,w,3].  No host synchronisation."""
+        depth, poses, Ks, Ks_inv, nn_ids = self._fuse_inputs(depth, poses, Ks, nn_ids, Ks_inv)
+        n, h, w = depth.shape
+        count, fd, bits = consistency['count'], consistency['fused_depth'], consistency['consistent_bits']
+        assert count.dtype == torch.uint8 and fd.dtype == torch.float32 and bits.dtype == torch.int32
+        assert all(t.shape == (n, h, w) and t.is_contiguous() and t.device == self.device for t in (count, fd, bits))
+        rgb = None
+        if 'colour' in outputs:
+            rgb = self._f32(torch.as_tensor(imgs))
+            assert rgb.shape == (n, 3, h, w)
+        if taken is not None:
+            assert taken.dtype == torch.uint8 and taken.shape == (n, h, w) and taken.is_contiguous() and taken.device == self.device
+        out = {'emit': self.empty(h, w, dtype=torch.uint8), 'xyz': self.empty(h, w, 3)}
+        for k in ('colour', 'normal'):
+            if k in outputs:
+                out[k] = self.empty(h, w, 3)
+        ptr = lambda k: out[k].data_ptr() if k in out else None     # noqa: E731
+        a = _lib.NeurayFuseViewArgs(depth.data_ptr(), poses.data_ptr(), Ks.data_ptr(), Ks_inv.data_ptr(), nn_ids.data_ptr(), count.data_ptr(),
+                                    fd.data_ptr(), bits.data_ptr(), rgb.data_ptr() if rgb is not None else None,
+                                    taken.data_ptr() if taken is not None else None, out['emit'].data_ptr(), out['xyz'].data_ptr(), ptr('colour'),
+                                    ptr('normal'), n, h, w, nn_ids.shape[1], int(view), int(min_views), int(taken is not None), 0, float(tau_n), 0.0)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_fuse_view(C.byref(a), self._stream()))
+        self._event_done(ev, 'fuse_view', h * w)
+        return out
+
     def direct_render_rays_backward(self, alpha, colors, d_pixel, d_hit_prob=None):
         """Backward of direct_render's ray kernel: alpha [rn,dn] (logits), colors [rn,dn,3] (the SH colours), d_pixel [rn,3], d_hit_prob
         [rn,dn] or None -> (d_alpha [rn,dn], d_colors [rn,dn,3])"""

@@ -35,7 +35,7 @@ def resources(extra=()):
 def main():
     extra = [a for a in sys.argv[1:] if a.startswith('-D')]
     filt = sys.argv[sys.argv.index('--filter') + 1] if '--filter' in sys.argv else ''
-    rows = [r for r in resources(extra) if filt in r['name']]
+    rows = [r for r in resources(extra) if filt.lower() in r['name'].lower()]      # (the whole signature, any case)
     print('%-100s %5s %5s %6s %6s %8s %4s %7s' % ('kernel', 'VGPR', 'AGPR', 'vspill', 'sspill', 'scratch', 'occ', 'LDS'))
     for r in rows:
         name = re.sub(r'^void ', '', r['name'])

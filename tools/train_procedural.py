@@ -9,6 +9,10 @@ ground truth - a NeuralRayFtRenderer trained from scratch on one procedural scen
         trains every network of a NeuralRayFtRenderer on the scene's 42 training views (render + consistency loss of neuray_amd.loss, Adam),
         then renders the 6 held-out views with hip_arith f32 / x3 and the network coarse pass, and x3 with hip_coarse_pass = 'visibility':
         PSNR / SSIM (engine.image_metrics) against the ray-cast images and the rendered depth against the true depth.  One JSON line.
+        With --export-points the rendered depth of the training views is fused into a point cloud in each of the three modes
+        (neuray_amd/geometry.py) and the line gains, per mode, the point count, the mean / median distance of the points to the
+        true surface and the completeness at 2 x tau_d x mean depth: the share of the held-out views' back-projected true-depth pixels that
+        have a fused point within that radius.
 
 These numbers are about ONE procedurally generated scene and a model trained from scratch for minutes - not the paper's checkpoints."""
 import argparse
@@ -23,7 +27,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from neuray_amd import database, pipeline, procedural  # noqa: E402
+from neuray_amd import database, geometry, pipeline, procedural  # noqa: E402
 from neuray_amd.loss import name2loss, total_loss  # noqa: E402
 from neuray_amd.network import render_ops  # noqa: E402
 
@@ -129,6 +133,60 @@ def evaluate(ft, db, val_ids, dev):
     return res
 
 
+def within_radius(points, queries, radius):
+    """[q] bool: some point lies within `radius` of the query.  A voxel hash of cell size `radius` (sorted integer keys, searchsorted) finds
+    the candidates: the 27 cells around the query's cell; the distance is then checked exactly."""
+    lo = torch.minimum(points.min(0).values, queries.min(0).values) - radius
+    cell = lambda x: ((x - lo) / radius).floor().long()                    # noqa: E731
+    dims = cell(torch.maximum(points.max(0).values, queries.max(0).values)) + 2
+    key = lambda c: (c[:, 0] * dims[1] + c[:, 1]) * dims[2] + c[:, 2]      # noqa: E731
+    keys, order = torch.sort(key(cell(points)))
+    pts = points[order]
+    found = torch.zeros(queries.shape[0], dtype=torch.bool, device=queries.device)
+    qc = cell(queries)
+    width = int(torch.unique_consecutive(keys, return_counts=True)[1].max()) if keys.numel() else 0
+    for dx in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dz in (-1, 0, 1):
+                k = key(qc + torch.tensor([dx, dy, dz], device=qc.device))
+                start = torch.searchsorted(keys, k)
+                for o in range(width):                                      # (at most `width` points share a cell)
+                    i = (start + o).clamp(max=keys.numel() - 1)
+                    hit = (keys[i] == k) & (start + o < keys.numel())
+                    found |= hit & (((pts[i] - queries) ** 2).sum(-1) <= radius * radius)
+    return found
+
+
+def export_points(ft, db, train_ids, val_ids, dev, tau_d=0.01):
+    """the rendered depth of the training views, fused, in the three render modes -> {mode: {points, surface_mean, surface_median,
+    completeness, radius}}"""
+    from neuray_amd.engine import host_inverse
+    val = geometry.database_depth_maps(db, val_ids)
+    d = torch.from_numpy(val['depth']).to(dev)
+    n, h, w = d.shape
+    ys, xs = torch.meshgrid(torch.arange(h, device=dev), torch.arange(w, device=dev), indexing='ij')
+    pix = torch.stack([xs, ys, torch.ones_like(xs)], -1).float()
+    Ki, P = host_inverse(torch.from_numpy(val['Ks'])).to(dev), torch.from_numpy(val['poses']).to(dev)
+    cam = torch.einsum('nij,hwj->nhwi', Ki, pix) * d[..., None]
+    truth = torch.einsum('nji,nhwj->nhwi', P[:, :, :3], cam - P[:, None, None, :, 3])[d > 0]         # R^T (K^-1 [x,y,1] d - t)
+    radius = 2 * tau_d * float(d[d > 0].mean())
+    res = {}
+    ft.eval()
+    for tag, arith, coarse in (('f32_network', 'f32', 'network'), ('x3_network', 'x3', 'network'), ('x3_visibility', 'x3', 'visibility')):
+        ft.cfg['hip_arith'], ft.cfg['hip_coarse_pass'] = arith, coarse
+        ft.__dict__['_engine'] = None
+        maps = geometry.render_depth_maps(ft, db, train_ids)
+        cloud = geometry.fuse_points(maps['depth'], maps['imgs'], maps['poses'], maps['Ks'], tau_d=tau_d)
+        m = int(cloud['points'].shape[0])
+        rec = {'points': m, 'radius': radius, 'surface_mean': None, 'surface_median': None, 'completeness': 0.0}
+        if m:
+            dist = geometry.surface_distance(db.scene, cloud['points'])
+            rec.update(surface_mean=float(dist.mean()), surface_median=float(np.median(dist)),
+                       completeness=float(within_radius(cloud['points'].to(dev), truth, radius).float().mean()))
+        res[tag] = rec
+    return res
+
+
 def train(args, dev):
     db = database.parse_database_name(args.scene)
     train_ids, val_ids = database.get_database_split(db, 'val_all')
@@ -160,6 +218,8 @@ def train(args, dev):
            'rays_per_step': args.rays, 'lr': args.lr, 'data_s': t_data, 'train_s': t_train, 'ms_per_step': 1e3 * t_train / max(args.steps, 1),
            'loss_rgb_nr_fine': curve, 'modes': evaluate(ft, db, val_ids, dev),
            'what': 'one procedurally generated scene, every network trained from scratch for minutes: not the paper\'s checkpoints'}
+    if args.export_points:
+        res['export_points'] = export_points(ft, db, train_ids, val_ids, dev)
     return res
 
 
@@ -171,6 +231,7 @@ def main():
     ap.add_argument('--rays', type=int, default=512)
     ap.add_argument('--lr', type=float, default=1e-3)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--export-points', action='store_true', help='fuse the rendered depth of the training views in each render mode')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     if args.time:
