@@ -754,6 +754,66 @@ typedef struct NeurayFuseViewArgs {
 } NeurayFuseViewArgs;
 int neuray_fuse_view(const NeurayFuseViewArgs* args, void* stream);
 
+/* ---- mesh export (neuray_amd/mesh.py; added within ABI 11: everything above is unchanged).  Volumetric fusion of posed depth
+ * maps and surface-nets extraction, the fp32 library only (the bf16-operand variants return an error), inference only.  Lattice point (ix, iy,
+ * iz), 0 <= i < (nx, ny, nz), sits at origin + (ix, iy, iz) * voxel_size; arrays are [nz][ny][nx], x fastest, colour planar [3][nz][ny][nx];
+ * every dimension >= 2 and nx * ny * nz <= 2^30.  The state of a volume is sums, all float32, zeroed once by the caller: tsum, w, csum[3], cw.
+ * neuray_tsdf_integrate adds the views [v0, v1) in ascending order: Pc = R_i p + t_i, z = Pc.z, q = K_i Pc, (un, vn) = floor(q.xy / q.z +
+ * 0.5) (pixel centres at integer coordinates, the NEAREST texel); skip unless z > 0, the texel inside the image and d = D_i[vn][un] > 0; sdf =
+ * d - z; skip if sdf < -trunc; tsum += min(sdf / trunc, 1), w += 1; if sdf <= trunc: csum[c] += rgb_i[c][vn][un], cw += 1.  rgb_dev, csum_dev
+ * and cw_dev may be NULL (all three).  No atomics: [0, n) in one call and in any split into consecutive calls give the same bits.
+ * Surface nets: f = tsum / w; a lattice point is inside where f < 0; cell (cx, cy, cz), 0 <= c < n - 1, is valid where its 8 corners have w >=
+ * min_weight (> 0) and active where it is valid and its corners are not all on one side.  neuray_surface_cells writes one byte per cell
+ * [nz-1][ny-1][nx-1]: bit 0 active; bits 1..3: the cell emits the quad of the lattice edge from its corner (cx, cy, cz) towards +x / +y / +z
+ * (the edge's ends differ in `inside`, and the four cells around it - for axis a, (a, b, c) cyclic, at offsets (b-1, c-1), (b, c-1), (b, c),
+ * (b-1, c) - exist and are valid).  vert_offset_dev / quad_offset_dev [cells] int64: the exclusive prefix sums of bit 0 and of the number of
+ * quad bits over the cell index; n_vertices / n_quads their totals.  neuray_surface_emit writes per active cell, into its slot: the vertex
+ * origin + (cell + m) * voxel_size, m the mean of the crossing points (t = f_lo / (f_lo - f_hi)) of the cell's edges whose ends differ in
+ * `inside`; the normal (the normalised sums of the forward differences of f over the four edges per axis: towards free space; zero for a zero
+ * vector); the colour (sum of csum / sum of cw over the corners; 0.5 where that is 0 / 0 or csum_dev is NULL); and per quad bit, ordered by
+ * owner cell then axis, the triangles (v0, v1, v2), (v0, v2, v3) of the four cells' vertex indices (int32) in the order above where the edge's
+ * low end is inside, in reversed order otherwise. */
+typedef struct NeurayTsdfIntegrateArgs {
+    const float* depth_dev;            /* [n][h][w] */
+    const float* rgb_dev;              /* [n][3][h][w] or NULL */
+    const float* poses_dev;            /* [n][3][4] world -> camera */
+    const float* Ks_dev;               /* [n][3][3] */
+    float* tsum_dev;
+    float* w_dev;
+    float* csum_dev;                   /* or NULL */
+    float* cw_dev;                     /* or NULL */
+    float origin_x, origin_y, origin_z, voxel_size, trunc, reserved_f;
+    int nx, ny, nz, n, h, w, v0, v1;
+} NeurayTsdfIntegrateArgs;
+int neuray_tsdf_integrate(const NeurayTsdfIntegrateArgs* args, void* stream);
+
+typedef struct NeuraySurfaceCellsArgs {
+    const float* tsum_dev;
+    const float* w_dev;
+    unsigned char* cells_dev;
+    int nx, ny, nz, reserved;
+    float min_weight, reserved_f;
+} NeuraySurfaceCellsArgs;
+int neuray_surface_cells(const NeuraySurfaceCellsArgs* args, void* stream);
+
+typedef struct NeuraySurfaceEmitArgs {
+    const float* tsum_dev;
+    const float* w_dev;
+    const float* csum_dev;             /* or NULL (with cw_dev) */
+    const float* cw_dev;
+    const unsigned char* cells_dev;
+    const long long* vert_offset_dev;  /* [cells] int64 */
+    const long long* quad_offset_dev;
+    float* vertices_dev;               /* [n_vertices][3] */
+    float* normals_dev;                /* [n_vertices][3] */
+    float* colours_dev;                /* [n_vertices][3] */
+    int* faces_dev;                    /* [2 n_quads][3] */
+    unsigned n_vertices, n_quads;
+    float origin_x, origin_y, origin_z, voxel_size;
+    int nx, ny, nz, reserved;
+} NeuraySurfaceEmitArgs;
+int neuray_surface_emit(const NeuraySurfaceEmitArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,25 @@ class NeurayFuseViewArgs(C.Structure):
         [(n, C.c_int) for n in ('n', 'h', 'w', 'n_src', 'view', 'min_views', 'dedup', 'reserved')] + [('tau_n', C.c_float), ('reserved_f', C.c_float)]
 
 
+class NeurayTsdfIntegrateArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('depth_dev', 'rgb_dev', 'poses_dev', 'Ks_dev', 'tsum_dev', 'w_dev', 'csum_dev', 'cw_dev')] + \
+        [(n, C.c_float) for n in ('origin_x', 'origin_y', 'origin_z', 'voxel_size', 'trunc', 'reserved_f')] + \
+        [(n, C.c_int) for n in ('nx', 'ny', 'nz', 'n', 'h', 'w', 'v0', 'v1')]
+
+
+class NeuraySurfaceCellsArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('tsum_dev', 'w_dev', 'cells_dev')] + [(n, C.c_int) for n in ('nx', 'ny', 'nz', 'reserved')] + \
+        [('min_weight', C.c_float), ('reserved_f', C.c_float)]
+
+
+class NeuraySurfaceEmitArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('tsum_dev', 'w_dev', 'csum_dev', 'cw_dev', 'cells_dev', 'vert_offset_dev', 'quad_offset_dev',
+                                          'vertices_dev', 'normals_dev', 'colours_dev', 'faces_dev')] + \
+        [('n_vertices', C.c_uint), ('n_quads', C.c_uint)] + [(n, C.c_float) for n in ('origin_x', 'origin_y', 'origin_z', 'voxel_size')] + \
+        [(n, C.c_int) for n in ('nx', 'ny', 'nz', 'reserved')]
+
+
+TSDF_MAX_POINTS = 1 << 30      # nx * ny * nz of a volume (include/neuray_hip.h)
 FUSE_MAX_SRC = 16              # include/neuray_hip.h NEURAY_FUSE_MAX_SRC
 PROC_HEADER, PROC_PRIM, PROC_MAX_PRIMS = 16, 48, 32   # the scene array of neuray_procedural_render (include/neuray_hip.h NEURAY_PROC_*)
 LOSS_RENDER, LOSS_CONSIST, LOSS_DEPTH = 0, 1, 2   # NeurayLossTerm.kind (include/neuray_hip.h NEURAY_LOSS_*)
@@ -253,6 +272,10 @@ SYMBOLS = {
     # geometry export
     'neuray_depth_consistency': (C.c_int, [C.POINTER(NeurayDepthConsistencyArgs), C.c_void_p]),
     'neuray_fuse_view': (C.c_int, [C.POINTER(NeurayFuseViewArgs), C.c_void_p]),
+    # mesh export
+    'neuray_tsdf_integrate': (C.c_int, [C.POINTER(NeurayTsdfIntegrateArgs), C.c_void_p]),
+    'neuray_surface_cells': (C.c_int, [C.POINTER(NeuraySurfaceCellsArgs), C.c_void_p]),
+    'neuray_surface_emit': (C.c_int, [C.POINTER(NeuraySurfaceEmitArgs), C.c_void_p]),
     'neuray_inorm_backward_det': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 7),
 }
 

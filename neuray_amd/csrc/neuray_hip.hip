@@ -21,6 +21,7 @@
 #ifndef NR_BF16_QUADS
 #include "nr_kernels_vis.h"         // (fp32 MFMA only: the bf16-operand builds leave the visibility entries returning an error)
 #include "nr_kernels_fuse.h"        // (the fp32 library only, like the visibility entries)
+#include "nr_kernels_tsdf.h"        // (likewise)
 #endif
 #include "nr_pack.h"
 #include "../../include/neuray_hip.h"
@@ -1451,6 +1452,89 @@ int neuray_fuse_view(const NeurayFuseViewArgs* a, void* stream) {
     const dim3 grid((unsigned)((a->w + nr::kFuseTileX - 1) / nr::kFuseTileX), (unsigned)((a->h + nr::kFuseTileY - 1) / nr::kFuseTileY), 1u);
     NR_LAUNCH(nr::fuse_view_kernel, grid, dim3(nr::kFuseTileX * nr::kFuseTileY), 0, stream, p);
     return check_launch("neuray_fuse_view");
+#endif
+}
+
+// ---- mesh export ----
+#ifndef NR_BF16_QUADS
+// the lattice of a volume: every dimension >= 2, at most 2^30 points
+static int tsdf_dims(const char* who, int nx, int ny, int nz) {
+    if (nx < 2 || ny < 2 || nz < 2) return fail("%s: bad dims nx=%d ny=%d nz=%d (each at least 2)", who, nx, ny, nz);
+    if ((long long)nx * ny * nz > (1LL << 30)) return fail("%s: nx*ny*nz=%lld lattice points (at most 2^30)", who, (long long)nx * ny * nz);
+    return 0;
+}
+// the tiles per row (bx) and per slice (by) of a box of (ex, ey, ez) elements -> the number of workgroups (bx * by * ez <= ex * ey * ez <= 2^30)
+static unsigned tsdf_grid(int ex, int ey, int ez, int& bx, int& by) {
+    bx = (ex + nr::kTsdfTileX - 1) / nr::kTsdfTileX; by = (ey + nr::kTsdfTileY - 1) / nr::kTsdfTileY;
+    return (unsigned)((long long)bx * by * ez);
+}
+#endif
+
+int neuray_tsdf_integrate(const NeurayTsdfIntegrateArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_tsdf_integrate: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_tsdf_integrate: null args");
+    if (int rc = tsdf_dims("neuray_tsdf_integrate", a->nx, a->ny, a->nz)) return rc;
+    if (a->n < 1 || a->h < 1 || a->w < 1) return fail("neuray_tsdf_integrate: bad size n=%d h=%d w=%d", a->n, a->h, a->w);
+    if ((long long)a->h * a->w > 0x7fffffffLL) return fail("neuray_tsdf_integrate: h*w too large (a texel index is an int)");
+    if (a->v0 < 0 || a->v1 > a->n || a->v0 > a->v1) return fail("neuray_tsdf_integrate: views [%d,%d) outside [0,%d)", a->v0, a->v1, a->n);
+    if (!(a->voxel_size > 0.0f) || !(a->trunc > 0.0f)) return fail("neuray_tsdf_integrate: voxel_size and trunc must be positive (voxel_size=%g trunc=%g)", a->voxel_size, a->trunc);
+    if (!a->depth_dev || !a->poses_dev || !a->Ks_dev || !a->tsum_dev || !a->w_dev) return fail("neuray_tsdf_integrate: depth / poses / Ks / tsum / w missing");
+    const int colour = (a->rgb_dev != nullptr) + (a->csum_dev != nullptr) + (a->cw_dev != nullptr);
+    if (colour != 0 && colour != 3) return fail("neuray_tsdf_integrate: rgb, csum and cw go together (all or none)");
+    if (a->v0 == a->v1) return 0;
+    nr::TsdfIntegrateParams p;
+    p.depth = a->depth_dev; p.rgb = a->rgb_dev; p.poses = a->poses_dev; p.Ks = a->Ks_dev;
+    p.tsum = a->tsum_dev; p.wsum = a->w_dev; p.csum = a->csum_dev; p.cw = a->cw_dev;
+    p.ox = a->origin_x; p.oy = a->origin_y; p.oz = a->origin_z; p.vs = a->voxel_size; p.trunc = a->trunc;
+    p.nx = a->nx; p.ny = a->ny; p.nz = a->nz; p.h = a->h; p.w = a->w; p.v0 = a->v0; p.v1 = a->v1;
+    const unsigned blocks = tsdf_grid(a->nx, a->ny, a->nz, p.bx, p.by);
+    NR_LAUNCH(nr::tsdf_integrate_kernel, dim3(blocks), dim3(nr::kTsdfTileX * nr::kTsdfTileY), 0, stream, p);
+    return check_launch("neuray_tsdf_integrate");
+#endif
+}
+
+int neuray_surface_cells(const NeuraySurfaceCellsArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_surface_cells: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_surface_cells: null args");
+    if (int rc = tsdf_dims("neuray_surface_cells", a->nx, a->ny, a->nz)) return rc;
+    if (!(a->min_weight > 0.0f)) return fail("neuray_surface_cells: min_weight=%g must be positive", a->min_weight);
+    if (!a->tsum_dev || !a->w_dev || !a->cells_dev) return fail("neuray_surface_cells: tsum / w / cells missing");
+    nr::SurfaceCellsParams p;
+    p.tsum = a->tsum_dev; p.wsum = a->w_dev; p.cells = a->cells_dev; p.nx = a->nx; p.ny = a->ny; p.nz = a->nz; p.min_weight = a->min_weight;
+    const unsigned blocks = tsdf_grid(a->nx - 1, a->ny - 1, a->nz - 1, p.bx, p.by);
+    NR_LAUNCH(nr::surface_cells_kernel, dim3(blocks), dim3(nr::kTsdfTileX * nr::kTsdfTileY), 0, stream, p);
+    return check_launch("neuray_surface_cells");
+#endif
+}
+
+int neuray_surface_emit(const NeuraySurfaceEmitArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_surface_emit: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_surface_emit: null args");
+    if (int rc = tsdf_dims("neuray_surface_emit", a->nx, a->ny, a->nz)) return rc;
+    if (!(a->voxel_size > 0.0f)) return fail("neuray_surface_emit: voxel_size=%g must be positive", a->voxel_size);
+    if (a->n_vertices > (1u << 30) || a->n_quads > 3u * (1u << 30)) return fail("neuray_surface_emit: bad totals n_vertices=%u n_quads=%u", a->n_vertices, a->n_quads);
+    if (!a->tsum_dev || !a->w_dev || !a->cells_dev || !a->vert_offset_dev || !a->quad_offset_dev) return fail("neuray_surface_emit: tsum / w / cells / offsets missing");
+    if ((a->csum_dev != nullptr) != (a->cw_dev != nullptr)) return fail("neuray_surface_emit: csum and cw go together");
+    if (a->n_vertices == 0) return 0;
+    if (!a->vertices_dev || !a->normals_dev || !a->colours_dev || (a->n_quads > 0 && !a->faces_dev)) return fail("neuray_surface_emit: vertices / normals / colours / faces missing");
+    nr::SurfaceEmitParams p;
+    p.tsum = a->tsum_dev; p.wsum = a->w_dev; p.csum = a->csum_dev; p.cw = a->cw_dev; p.cells = a->cells_dev;
+    p.vert_offset = a->vert_offset_dev; p.quad_offset = a->quad_offset_dev;
+    p.vertices = a->vertices_dev; p.normals = a->normals_dev; p.colours = a->colours_dev; p.faces = a->faces_dev;
+    p.n_vertices = a->n_vertices; p.n_quads = a->n_quads;
+    p.ox = a->origin_x; p.oy = a->origin_y; p.oz = a->origin_z; p.vs = a->voxel_size; p.nx = a->nx; p.ny = a->ny; p.nz = a->nz;
+    const unsigned blocks = tsdf_grid(a->nx - 1, a->ny - 1, a->nz - 1, p.bx, p.by);
+    NR_LAUNCH(nr::surface_emit_kernel, dim3(blocks), dim3(nr::kTsdfTileX * nr::kTsdfTileY), 0, stream, p);
+    return check_launch("neuray_surface_emit");
 #endif
 }
 

@@ -1065,6 +1065,81 @@ class RenderEngine:
         self._event_done(ev, 'fuse_view', h * w)
         return out
 
+    # ---- mesh export (neuray_amd/mesh.py) ----
+    def _tsdf_state(self, state, dims):
+        """state: dict of device tensors tsum / w [nz,ny,nx] and optionally csum [3,nz,ny,nx] / cw [nz,ny,nx] -> (nx, ny, nz), has colour"""
+        if self.variant != 'fp32':
+            raise NotImplementedError("neuray_amd: the mesh export lives in the fp32 library (variant=%r)" % (self.variant,))
+        nx, ny, nz = (int(d) for d in dims)
+        colour = state.get('csum') is not None
+        shapes = {'tsum': (nz, ny, nx), 'w': (nz, ny, nx)}
+        if colour:
+            shapes.update(csum=(3, nz, ny, nx), cw=(nz, ny, nx))
+        for k, shape in shapes.items():
+            t = state[k]
+            assert t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == self.device, \
+                "%s: float32 %s on %s, contiguous" % (k, shape, self.device)
+        return (nx, ny, nz), colour
+
+    def tsdf_integrate(self, state, origin, voxel_size, trunc, dims, depth, imgs, poses, Ks, views=None):
+        """Adds the views [v0, v1) (None: all) of posed depth maps to a volume's sums in place (include/neuray_hip.h,
+        neuray_tsdf_integrate).  state: dict of device tensors tsum / w [nz,ny,nx] and, for colour, csum [3,nz,ny,nx] / cw [nz,ny,nx], zeroed
+        once by the caller; depth [n,h,w], imgs [n,3,h,w] (unused without colour state), poses [n,3,4], Ks [n,3,3].  No host synchronisation."""
+        (nx, ny, nz), colour = self._tsdf_state(state, dims)
+        depth = self._f32(torch.as_tensor(depth))
+        if depth.dim() == 4:
+            depth = depth[:, 0].contiguous()
+        poses = self._f32(torch.as_tensor(poses)).reshape(-1, 3, 4)
+        Ks = self._f32(torch.as_tensor(Ks)).reshape(-1, 3, 3)
+        n = poses.shape[0]
+        assert depth.dim() == 3 and depth.shape[0] == n and Ks.shape[0] == n, "depth [n,h,w] and Ks [n,3,3] for %d poses" % n
+        h, w = depth.shape[1:]
+        rgb = None
+        if colour:
+            rgb = self._f32(torch.as_tensor(imgs))
+            assert rgb.shape == (n, 3, h, w), "imgs [n,3,h,w]: %s" % (tuple(rgb.shape),)
+        v0, v1 = (0, n) if views is None else (int(views[0]), int(views[1]))
+        a = _lib.NeurayTsdfIntegrateArgs(depth.data_ptr(), rgb.data_ptr() if colour else None, poses.data_ptr(), Ks.data_ptr(),
+                                         state['tsum'].data_ptr(), state['w'].data_ptr(), state['csum'].data_ptr() if colour else None,
+                                         state['cw'].data_ptr() if colour else None, float(origin[0]), float(origin[1]), float(origin[2]),
+                                         float(voxel_size), float(trunc), 0.0, nx, ny, nz, n, h, w, v0, v1)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_tsdf_integrate(C.byref(a), self._stream()))
+        self._event_done(ev, 'tsdf_integrate', nx * ny * nz * max(v1 - v0, 0))
+        return state
+
+    def surface_cells(self, state, dims, min_weight=1.0):
+        """One byte per cell of a volume (neuray_surface_cells): bit 0 active, bits 1..3 the quads it owns -> uint8 [nz-1,ny-1,nx-1]"""
+        (nx, ny, nz), _ = self._tsdf_state(state, dims)
+        cells = self.empty(max(nz - 1, 0), max(ny - 1, 0), max(nx - 1, 0), dtype=torch.uint8)
+        a = _lib.NeuraySurfaceCellsArgs(state['tsum'].data_ptr(), state['w'].data_ptr(), cells.data_ptr(), nx, ny, nz, 0, float(min_weight), 0.0)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_surface_cells(C.byref(a), self._stream()))
+        self._event_done(ev, 'surface_cells', cells.numel())
+        return cells
+
+    def surface_emit(self, state, origin, voxel_size, dims, cells):
+        """The mesh of a volume given its cell bytes (neuray_surface_emit) -> dict of device tensors vertices / normals / colors [m,3]
+        float32 and faces [k,3] int32.  The offsets are prefix sums on the device; ONE read-back, of the two totals."""
+        (nx, ny, nz), colour = self._tsdf_state(state, dims)
+        assert cells.dtype == torch.uint8 and tuple(cells.shape) == (nz - 1, ny - 1, nx - 1) and cells.is_contiguous() and cells.device == self.device
+        flat = cells.reshape(-1)
+        is_vertex = (flat & 1).to(torch.int64)
+        quads = (((flat >> 1) & 1) + ((flat >> 2) & 1) + ((flat >> 3) & 1)).to(torch.int64)
+        vert_incl, quad_incl = torch.cumsum(is_vertex, 0), torch.cumsum(quads, 0)
+        totals = torch.stack([vert_incl[-1], quad_incl[-1]]).cpu()
+        m, k = int(totals[0]), int(totals[1])
+        vert_off, quad_off = (vert_incl - is_vertex).contiguous(), (quad_incl - quads).contiguous()
+        out = {'vertices': self.empty(m, 3), 'normals': self.empty(m, 3), 'colors': self.empty(m, 3), 'faces': self.empty(2 * k, 3, dtype=torch.int32)}
+        a = _lib.NeuraySurfaceEmitArgs(state['tsum'].data_ptr(), state['w'].data_ptr(), state['csum'].data_ptr() if colour else None,
+                                       state['cw'].data_ptr() if colour else None, cells.data_ptr(), vert_off.data_ptr(), quad_off.data_ptr(),
+                                       out['vertices'].data_ptr(), out['normals'].data_ptr(), out['colors'].data_ptr(), out['faces'].data_ptr(),
+                                       m, k, float(origin[0]), float(origin[1]), float(origin[2]), float(voxel_size), nx, ny, nz, 0)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_surface_emit(C.byref(a), self._stream()))
+        self._event_done(ev, 'surface_emit', flat.numel())
+        return out
+
     def direct_render_rays_backward(self, alpha, colors, d_pixel, d_hit_prob=None):
         """Backward of direct_render's ray kernel: alpha [rn,dn] (logits), colors [rn,dn,3] (the SH colours), d_pixel [rn,3], d_hit_prob
         [rn,dn] or None -> (d_alpha [rn,dn], d_colors [rn,dn,3])"""
