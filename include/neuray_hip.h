@@ -814,6 +814,51 @@ typedef struct NeuraySurfaceEmitArgs {
 } NeuraySurfaceEmitArgs;
 int neuray_surface_emit(const NeuraySurfaceEmitArgs* args, void* stream);
 
+/* ---- ray casting of a volume (neuray_amd/mesh.py; added within ABI 11: everything above is unchanged).  The fp32 library
+ * only, inference only.  neuray_surface_blocks reduces the cell bytes of neuray_surface_cells to one byte per block of 8 x 8 x 8 cells,
+ * [bz][by][bx] with b = ceil((n - 1) / 8): 1 where a cell of the block or within one cell of it has bit 0 set, else 0.
+ * neuray_tsdf_raycast: per view i < n and pixel (x, y) (pixel centres at integers) the first zero crossing of the field along the pixel's ray.
+ *   field_dev: f = tsum / w [nz][ny][nx], NaN where the lattice point is unknown (w < min_weight); csum_dev / cw_dev: the colour sums of the
+ *     volume or NULL (both).  rays_dev [n][12]: M = R^T K^-1 row-major, then c = -R^T t.  depth_range_dev [n][2] near, far or NULL: [0, inf).
+ *   ray: d[a] = (M[a][0] x + M[a][1] y) + M[a][2]; the point at z-depth s is c + s d; in lattice units g[a](s) = g0[a] + s gd[a], g0[a] =
+ *     (c[a] - origin[a]) / voxel_size, gd[a] = d[a] / voxel_size.
+ *   interval [s_in, s_out]: [near, far] cut by the slabs 0 <= g[a] <= n[a] - 1 (an axis with gd[a] == 0 empties the ray where g0[a] is
+ *     outside its slab); empty unless s_in <= s_out: status 0.
+ *   samples: ds = (step * voxel_size) / |d|, 0 < step <= 0.95 (in voxels); s_k = s_in + k ds, k = 0 .. floor(min((s_out - s_in) / ds, 2^22)).
+ *   value at s: cell[a] = clamp(floor(g[a]), 0, n[a] - 2), t = g - cell; the trilinear combination of the 8 corners c_j (j = dz 4 + dy 2 +
+ *     dx) with lerp(p, q, t) = p + t (q - p) along x (pairs 01, 23, 45, 67), then y, then z; NaN (unknown) if any corner is.
+ *   first crossing: the first k with samples k - 1 and k both known and (f_{k-1} < 0) != (f_k < 0).  f_k < 0: status 1, depth = s_{k-1} + ds
+ *     (f_{k-1} / (f_{k-1} - f_k)); else status 2 (the surface seen from behind) and depth 0.  No crossing: status 0, depth 0.
+ *   at a hit, in the cell of g(depth) where all its corners are known, else at sample k in its cell: normal = the gradient of the
+ *     trilinear interpolant, normalised (towards free space; zero for a zero gradient); colour = trilinear csum / trilinear cw, 0.5 where
+ *     that denominator is not positive or csum_dev is NULL.  Pixels without a hit get zero normals and colours.
+ *   blocks_dev (neuray_surface_blocks of the same volume and min_weight) or NULL: samples in blocks whose byte is 0 are skipped; this
+ *     changes no bit of depth, normal, colours or status, only evaluated_dev: the number of field samples evaluated.
+ *   normal_dev, colours_dev [n][3][h][w] and evaluated_dev [n][h][w] may be NULL: not written.  n <= 65535, h * w < 2^31. */
+typedef struct NeuraySurfaceBlocksArgs {
+    const unsigned char* cells_dev;    /* [nz-1][ny-1][nx-1] */
+    unsigned char* blocks_dev;         /* [bz][by][bx] */
+    int nx, ny, nz, reserved;
+} NeuraySurfaceBlocksArgs;
+int neuray_surface_blocks(const NeuraySurfaceBlocksArgs* args, void* stream);
+
+typedef struct NeurayTsdfRaycastArgs {
+    const float* field_dev;
+    const float* csum_dev;             /* or NULL (with cw_dev) */
+    const float* cw_dev;
+    const float* rays_dev;             /* [n][12] */
+    const float* depth_range_dev;      /* [n][2] or NULL */
+    const unsigned char* blocks_dev;   /* or NULL */
+    float* depth_dev;                  /* [n][h][w] */
+    float* normal_dev;                 /* [n][3][h][w] or NULL */
+    float* colours_dev;                /* [n][3][h][w] or NULL */
+    unsigned char* status_dev;         /* [n][h][w] */
+    int* evaluated_dev;                /* [n][h][w] or NULL */
+    float origin_x, origin_y, origin_z, voxel_size, step, reserved_f;
+    int nx, ny, nz, n, h, w, reserved, reserved2;
+} NeurayTsdfRaycastArgs;
+int neuray_tsdf_raycast(const NeurayTsdfRaycastArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,18 @@ class NeuraySurfaceEmitArgs(C.Structure):
         [(n, C.c_int) for n in ('nx', 'ny', 'nz', 'reserved')]
 
 
+class NeuraySurfaceBlocksArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('cells_dev', 'blocks_dev')] + [(n, C.c_int) for n in ('nx', 'ny', 'nz', 'reserved')]
+
+
+class NeurayTsdfRaycastArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('field_dev', 'csum_dev', 'cw_dev', 'rays_dev', 'depth_range_dev', 'blocks_dev', 'depth_dev',
+                                          'normal_dev', 'colours_dev', 'status_dev', 'evaluated_dev')] + \
+        [(n, C.c_float) for n in ('origin_x', 'origin_y', 'origin_z', 'voxel_size', 'step', 'reserved_f')] + \
+        [(n, C.c_int) for n in ('nx', 'ny', 'nz', 'n', 'h', 'w', 'reserved', 'reserved2')]
+
+
+TSDF_BLOCK = 8                 # cells per block and axis (neuray_surface_blocks)
 TSDF_MAX_POINTS = 1 << 30      # nx * ny * nz of a volume (include/neuray_hip.h)
 FUSE_MAX_SRC = 16              # include/neuray_hip.h NEURAY_FUSE_MAX_SRC
 PROC_HEADER, PROC_PRIM, PROC_MAX_PRIMS = 16, 48, 32   # the scene array of neuray_procedural_render (include/neuray_hip.h NEURAY_PROC_*)
@@ -276,6 +288,9 @@ SYMBOLS = {
     'neuray_tsdf_integrate': (C.c_int, [C.POINTER(NeurayTsdfIntegrateArgs), C.c_void_p]),
     'neuray_surface_cells': (C.c_int, [C.POINTER(NeuraySurfaceCellsArgs), C.c_void_p]),
     'neuray_surface_emit': (C.c_int, [C.POINTER(NeuraySurfaceEmitArgs), C.c_void_p]),
+    # ray casting of a volume
+    'neuray_surface_blocks': (C.c_int, [C.POINTER(NeuraySurfaceBlocksArgs), C.c_void_p]),
+    'neuray_tsdf_raycast': (C.c_int, [C.POINTER(NeurayTsdfRaycastArgs), C.c_void_p]),
     'neuray_inorm_backward_det': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 7),
 }
 

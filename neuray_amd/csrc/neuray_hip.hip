@@ -1538,6 +1538,50 @@ int neuray_surface_emit(const NeuraySurfaceEmitArgs* a, void* stream) {
 #endif
 }
 
+// ---- ray casting of a volume ----
+int neuray_surface_blocks(const NeuraySurfaceBlocksArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_surface_blocks: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_surface_blocks: null args");
+    if (int rc = tsdf_dims("neuray_surface_blocks", a->nx, a->ny, a->nz)) return rc;
+    if (!a->cells_dev || !a->blocks_dev) return fail("neuray_surface_blocks: cells / blocks missing");
+    nr::SurfaceBlocksParams p;
+    p.cells = a->cells_dev; p.blocks = a->blocks_dev; p.mx = a->nx - 1; p.my = a->ny - 1; p.mz = a->nz - 1;
+    p.bx = (p.mx + nr::kTsdfBlock - 1) / nr::kTsdfBlock; p.by = (p.my + nr::kTsdfBlock - 1) / nr::kTsdfBlock;
+    const int bz = (p.mz + nr::kTsdfBlock - 1) / nr::kTsdfBlock;
+    NR_LAUNCH(nr::surface_blocks_kernel, dim3((unsigned)(p.bx * p.by * bz)), dim3(64), 0, stream, p);          // (at most 2^21 blocks)
+    return check_launch("neuray_surface_blocks");
+#endif
+}
+
+int neuray_tsdf_raycast(const NeurayTsdfRaycastArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_tsdf_raycast: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_tsdf_raycast: null args");
+    if (int rc = tsdf_dims("neuray_tsdf_raycast", a->nx, a->ny, a->nz)) return rc;
+    if (a->n < 1 || a->n > 65535 || a->h < 1 || a->w < 1) return fail("neuray_tsdf_raycast: bad size n=%d h=%d w=%d (n in 1 .. 65535, h and w positive)", a->n, a->h, a->w);
+    if ((long long)a->h * a->w > 0x7fffffffLL) return fail("neuray_tsdf_raycast: h*w too large (a pixel index is an int)");
+    if (!(a->voxel_size > 0.0f)) return fail("neuray_tsdf_raycast: voxel_size=%g must be positive", a->voxel_size);
+    if (!(a->step > 0.0f) || !(a->step <= 0.95f)) return fail("neuray_tsdf_raycast: step=%g outside (0, 0.95] voxels", a->step);
+    if (!a->field_dev || !a->rays_dev || !a->depth_dev || !a->status_dev) return fail("neuray_tsdf_raycast: field / rays / depth / status missing");
+    if ((a->csum_dev != nullptr) != (a->cw_dev != nullptr)) return fail("neuray_tsdf_raycast: csum and cw go together");
+    nr::TsdfRaycastParams p;
+    p.field = a->field_dev; p.csum = a->csum_dev; p.cw = a->cw_dev; p.rays = a->rays_dev; p.range = a->depth_range_dev; p.blocks = a->blocks_dev;
+    p.depth = a->depth_dev; p.normal = a->normal_dev; p.colours = a->colours_dev; p.status = a->status_dev; p.evaluated = a->evaluated_dev;
+    p.ox = a->origin_x; p.oy = a->origin_y; p.oz = a->origin_z; p.vs = a->voxel_size; p.step = a->step;
+    p.nx = a->nx; p.ny = a->ny; p.nz = a->nz; p.h = a->h; p.w = a->w;
+    p.bx = (a->nx - 1 + nr::kTsdfBlock - 1) / nr::kTsdfBlock; p.by = (a->ny - 1 + nr::kTsdfBlock - 1) / nr::kTsdfBlock;
+    const dim3 grid((unsigned)((a->w + nr::kRaycastTileX - 1) / nr::kRaycastTileX), (unsigned)((a->h + nr::kRaycastTileY - 1) / nr::kRaycastTileY), (unsigned)a->n);
+    if (grid.y > 65535u) return fail("neuray_tsdf_raycast: h=%d too large (at most %d)", a->h, 65535 * nr::kRaycastTileY);
+    NR_LAUNCH(nr::tsdf_raycast_kernel, grid, dim3(nr::kRaycastTileX * nr::kRaycastTileY), 0, stream, p);
+    return check_launch("neuray_tsdf_raycast");
+#endif
+}
+
 #ifdef NR_B2_PROFILE
 // profile build only (tools/profile_bwd2.py): read (and optionally clear) the per-mark cycle sums of points_backward2_kernel
 int neuray_debug_b2_profile(unsigned long long* out, int clear) {

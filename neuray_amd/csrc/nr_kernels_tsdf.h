@@ -12,6 +12,36 @@
 //   Tsum += min(sdf / trunc, 1), W += 1;  if sdf <= trunc: Csum[c] += rgb_i[c][vn][un], Cw += 1
 // Surface nets: f = Tsum / W, a lattice point is inside where f < 0, a cell (its 8 corners (c + d), d in {0,1}^3) is valid where every corner
 // has W >= min_weight and active where it is valid and its corners are not all on one side.
+//
+// Ray casting (mesh.raycast_numpy): per view and pixel the first zero crossing of the field along the pixel's ray.
+//   field: f = Tsum / W in float32, NaN ("unknown") where W < min_weight - one elementwise pass of the caller, not of these kernels.  NaN
+//     is exact here: the library is built without any fast-math flag, so x == x is false exactly for NaN and NaN propagates through + - *.
+//   ray of pixel (x, y) of view i (pixel centres at integers): the 12 floats M = R^T K^-1 (row-major), c = -R^T t, made in float64 and
+//     rounded; d[a] = (M[a][0] * x + M[a][1] * y) + M[a][2]; the point at z-depth s is c + s d; in lattice units g[a](s) = g0[a] + s * gd[a]
+//     with g0[a] = (c[a] - origin[a]) / vs and gd[a] = d[a] / vs.
+//   interval: [s_in, s_out] starts as [near, far] (depth_range, default [0, inf)); per axis a with hi = n[a] - 1: if gd[a] == 0 the ray is
+//     empty where g0[a] < 0 or g0[a] > hi, else t1 = (0 - g0[a]) / gd[a], t2 = (hi - g0[a]) / gd[a], s_in = max(s_in, min(t1, t2)), s_out =
+//     min(s_out, max(t1, t2)).  Empty unless s_in <= s_out: status 0.
+//   samples: ds = (step * vs) / sqrt((d0 d0 + d1 d1) + d2 d2) (a ray without 0 < ds < inf is empty); s_k = s_in + (float)k * ds for k = 0 ..
+//     floor(min((s_out - s_in) / ds, 2^22)).
+//   value at s: cell[a] = clamp(floor(g[a]), 0, n[a] - 2), t[a] = g[a] - cell[a]; with the corners c_j, j = dz * 4 + dy * 2 + dx, and
+//     lerp(p, q, t) = p + t * (q - p): x first, a_0..3 = lerp(c_0, c_1), lerp(c_2, c_3), lerp(c_4, c_5), lerp(c_6, c_7) at t[0]; then y,
+//     b_0 = lerp(a_0, a_1), b_1 = lerp(a_2, a_3) at t[1]; then z, lerp(b_0, b_1) at t[2].  NaN (unknown) if any corner is.
+//   first crossing: the first k whose samples k - 1 and k are both known (and both evaluated) with (f_{k-1} < 0) != (f_k < 0).  f_k < 0:
+//     status 1, depth = s_{k-1} + ds * (f_{k-1} / (f_{k-1} - f_k)); otherwise status 2 (the surface from behind), depth 0.  The ray ends
+//     there.  No crossing: status 0, depth 0.
+//   at a hit: the cell and t of g(depth) where all 8 of its corners are known, else those of sample k.  Normal: the gradient of the
+//     trilinear interpolant there - per axis the four corner differences along it (the other two offsets, in ascending axis order, running
+//     00, 10, 01, 11), lerped over the lower then the higher of the other two axes - divided by its length (zero where that is zero).
+//     Colour: the same trilinear combination of Csum[c] over that of Cw; 0.5 where that is not positive or there is no colour state.
+//   block skipping: `blocks` holds one byte per block of 8 x 8 x 8 cells, non-zero where a cell of the block or within one cell of it is
+//     active (surface_blocks_kernel).  A sample whose cell lies in an unflagged block is not evaluated and counts as unknown; k then moves
+//     to kn = max(k + 1, floor(clamp((s_exit - s_in) / ds, 0, kmax)) + 1), s_exit the smallest over the axes with gd[a] != 0 of ((gd[a] > 0 ?
+//     8 (b[a] + 1) : 8 b[a]) - g0[a]) / gd[a], provided the cell of sample kn - 1 lies in the same block b; if not, kn - 1 is tried the same
+//     way, and k + 1 is taken if that fails too.  The cell coordinates are monotone in k (every operation from k to the cell is monotone
+//     under rounding), so with samples k and kn - 1 in block b every sample between them is: only samples of unflagged blocks are skipped,
+//     whatever the rounding of s_exit.  Two samples that bracket a crossing lie in cells that share a corner (step < 1), one of those cells is
+//     active and the other within one cell of it: both blocks are flagged, both samples evaluated - no output bit depends on `blocks`.
 #pragma once
 #include "nr_kernels_fuse.h"
 
@@ -213,6 +243,212 @@ __global__ void __launch_bounds__(kTsdfTileX * kTsdfTileY) surface_emit_kernel(S
         o[0] = v0; o[1] = v1; o[2] = v2; o[3] = v0; o[4] = v2; o[5] = v3;
         q = q + 1;
     }
+}
+
+// ---- ray casting (the contract is at the head of this file) ----
+constexpr int kTsdfBlock = 8;                         // cells per block and axis
+constexpr int kRaycastMaxK = 1 << 22;
+#ifdef NR_RAYCAST_ROWS                                // a wave covers 64 x 1 pixels (the alternative measured in DESIGN.md 4.22)
+constexpr int kRaycastWaveX = 64, kRaycastWaveY = 1, kRaycastWavesX = 1, kRaycastWavesY = 4;
+#else                                                 // a wave covers 8 x 8 pixels, a workgroup 2 x 2 of them
+constexpr int kRaycastWaveX = 8, kRaycastWaveY = 8, kRaycastWavesX = 2, kRaycastWavesY = 2;
+#endif
+constexpr int kRaycastTileX = kRaycastWaveX * kRaycastWavesX, kRaycastTileY = kRaycastWaveY * kRaycastWavesY;
+
+struct SurfaceBlocksParams {
+    const unsigned char* cells;        // [nz-1][ny-1][nx-1]
+    unsigned char* blocks;             // [bz][by][bx], b = ceil((n - 1) / 8)
+    int mx, my, mz, bx, by;            // cells per axis; blocks per row and per slice
+};
+
+struct TsdfRaycastParams {
+    const float* field;        // [nz][ny][nx] f, NaN = unknown
+    const float* csum;         // [3][nz][ny][nx] (null: grey)
+    const float* cw;
+    const float* rays;         // [n][12]: M row-major, c
+    const float* range;        // [n][2] near, far (null: [0, inf))
+    const unsigned char* blocks;       // (null: every sample is evaluated)
+    float* depth;              // [n][h][w]
+    float* normal;             // [n][3][h][w] (may be null)
+    float* colours;            // [n][3][h][w] (may be null)
+    unsigned char* status;     // [n][h][w]
+    int* evaluated;            // [n][h][w] (may be null)
+    float ox, oy, oz, vs, step;
+    int nx, ny, nz, h, w, bx, by;
+};
+
+// One wave per block of 8 x 8 x 8 cells: the 64 lanes read the block's 10 x 10 x 10 neighbourhood of cell bytes clipped to the cell grid
+// (at most 1000 bytes, 16 rounds), a ballot combines them and lane 0 stores the byte.
+__global__ void __launch_bounds__(64) surface_blocks_kernel(SurfaceBlocksParams p) {
+    const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
+    const int bxi = b % p.bx, t = b / p.bx;
+    const int byi = t % p.by, bzi = t / p.by;
+    const int x0 = bxi * kTsdfBlock - 1, y0 = byi * kTsdfBlock - 1, z0 = bzi * kTsdfBlock - 1;
+    constexpr int kSide = kTsdfBlock + 2;
+    bool any = false;
+    for (int i = lane; i < kSide * kSide * kSide; i += 64) {
+        const int cx = x0 + i % kSide, cy = y0 + (i / kSide) % kSide, cz = z0 + i / (kSide * kSide);
+        if (cx >= 0 && cy >= 0 && cz >= 0 && cx < p.mx && cy < p.my && cz < p.mz)
+            any = any || (p.cells[((size_t)cz * p.my + cy) * p.mx + cx] & 1u) != 0u;
+    }
+    const bool flagged = __ballot(any) != 0ull;
+    if (lane == 0) p.blocks[b] = flagged ? 1 : 0;
+}
+
+struct TsdfRay { float g0x, g0y, g0z, gdx, gdy, gdz, s_in, ds; };
+
+__device__ __forceinline__ float tsdf_lerp(float a, float b, float t) { return a + t * (b - a); }
+
+__device__ __forceinline__ int tsdf_cell_of(float g, int cells, float& t) {
+    int c = (int)floorf(g);
+    c = c < 0 ? 0 : (c > cells - 1 ? cells - 1 : c);
+    t = g - (float)c;
+    return c;
+}
+
+// the (clamped) cell of the point at z-depth s and the point's offsets in it -> the index of the cell's corner 0
+__device__ __forceinline__ int tsdf_ray_cell(const TsdfRay& r, float s, int nx, int ny, int nz, int& cx, int& cy, int& cz, float& tx, float& ty,
+                                             float& tz) {
+    cx = tsdf_cell_of(r.g0x + s * r.gdx, nx - 1, tx);
+    cy = tsdf_cell_of(r.g0y + s * r.gdy, ny - 1, ty);
+    cz = tsdf_cell_of(r.g0z + s * r.gdz, nz - 1, tz);
+    return (cz * ny + cy) * nx + cx;
+}
+
+__device__ __forceinline__ void tsdf_corners(const float* __restrict__ a, int base, int nx, int ny, float (&c)[8]) {
+    NR_PRAGMA_UNROLL
+    for (int j = 0; j < 8; ++j) c[j] = a[(size_t)base + (size_t)((j >> 2) * ny + ((j >> 1) & 1)) * nx + (j & 1)];
+}
+
+__device__ __forceinline__ float tsdf_trilinear(const float (&c)[8], float tx, float ty, float tz) {
+    const float a0 = tsdf_lerp(c[0], c[1], tx), a1 = tsdf_lerp(c[2], c[3], tx), a2 = tsdf_lerp(c[4], c[5], tx), a3 = tsdf_lerp(c[6], c[7], tx);
+    return tsdf_lerp(tsdf_lerp(a0, a1, ty), tsdf_lerp(a2, a3, ty), tz);
+}
+
+__device__ __forceinline__ bool tsdf_same_block(const TsdfRay& r, int k, int nx, int ny, int nz, int bx, int by, int bz) {
+    int cx, cy, cz;
+    float tx, ty, tz;
+    tsdf_ray_cell(r, r.s_in + (float)k * r.ds, nx, ny, nz, cx, cy, cz, tx, ty, tz);
+    return (cx >> 3) == bx && (cy >> 3) == by && (cz >> 3) == bz;
+}
+
+// the z-depth at which the ray leaves the slab of block coordinate b along one axis (inf where it never does)
+__device__ __forceinline__ float tsdf_block_exit(float g0, float gd, int b) {
+    if (gd == 0.0f) return INFINITY;
+    return ((float)((gd > 0.0f ? b + 1 : b) * kTsdfBlock) - g0) / gd;
+}
+
+__global__ void __launch_bounds__(kRaycastTileX * kRaycastTileY) tsdf_raycast_kernel(TsdfRaycastParams p) {
+    const int view = (int)blockIdx.z;
+    const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
+    const int x = (int)blockIdx.x * kRaycastTileX + (wave % kRaycastWavesX) * kRaycastWaveX + lane % kRaycastWaveX;
+    const int y = (int)blockIdx.y * kRaycastTileY + (wave / kRaycastWavesX) * kRaycastWaveY + lane / kRaycastWaveX;
+    if (x >= p.w || y >= p.h) return;                 // (nothing below needs the whole wave)
+    const int nx = p.nx, ny = p.ny, nz = p.nz;
+    const float* __restrict__ f = p.field;
+    const float* __restrict__ cam = p.rays + (size_t)view * 12;        // (wave-uniform: scalar loads)
+    const float px = (float)x, py = (float)y;
+    const float dx = (cam[0] * px + cam[1] * py) + cam[2], dy = (cam[3] * px + cam[4] * py) + cam[5], dz = (cam[6] * px + cam[7] * py) + cam[8];
+    TsdfRay r;
+    r.g0x = (cam[9] - p.ox) / p.vs; r.g0y = (cam[10] - p.oy) / p.vs; r.g0z = (cam[11] - p.oz) / p.vs;
+    r.gdx = dx / p.vs; r.gdy = dy / p.vs; r.gdz = dz / p.vs;
+    float s_in = 0.0f, s_out = INFINITY;
+    if (p.range) { s_in = p.range[(size_t)view * 2]; s_out = p.range[(size_t)view * 2 + 1]; }
+    bool ok = true;
+    NR_PRAGMA_UNROLL
+    for (int a = 0; a < 3; ++a) {
+        const float g0 = a == 0 ? r.g0x : (a == 1 ? r.g0y : r.g0z), gd = a == 0 ? r.gdx : (a == 1 ? r.gdy : r.gdz);
+        const float hi = (float)((a == 0 ? nx : (a == 1 ? ny : nz)) - 1);
+        if (gd == 0.0f) {
+            if (g0 < 0.0f || g0 > hi) ok = false;
+        } else {
+            const float t1 = (0.0f - g0) / gd, t2 = (hi - g0) / gd;
+            s_in = fmaxf(s_in, fminf(t1, t2));
+            s_out = fminf(s_out, fmaxf(t1, t2));
+        }
+    }
+    r.s_in = s_in;
+    r.ds = (p.step * p.vs) / sqrtf((dx * dx + dy * dy) + dz * dz);
+    ok = ok && s_in <= s_out && r.ds > 0.0f && r.ds < INFINITY;
+    const int kmax = ok ? (int)floorf(fminf((s_out - s_in) / r.ds, (float)kRaycastMaxK)) : -1;
+    const unsigned char* __restrict__ blocks = p.blocks;
+    int k = 0, evaluated = 0, base = 0;
+    unsigned status = 0u;
+    float prev = NAN, cur = NAN, tx = 0.0f, ty = 0.0f, tz = 0.0f;
+    while (k <= kmax) {                               // (divergent by nature: rays end at different k)
+        int cx, cy, cz;
+        base = tsdf_ray_cell(r, s_in + (float)k * r.ds, nx, ny, nz, cx, cy, cz, tx, ty, tz);
+        if (blocks) {
+            const int bx = cx >> 3, by = cy >> 3, bz = cz >> 3;          // (kTsdfBlock = 8)
+            if (blocks[((size_t)bz * p.by + by) * p.bx + bx] == 0) {
+                const float s_exit = fminf(fminf(tsdf_block_exit(r.g0x, r.gdx, bx), tsdf_block_exit(r.g0y, r.gdy, by)), tsdf_block_exit(r.g0z, r.gdz, bz));
+                int kn = (int)floorf(fmaxf(fminf((s_exit - s_in) / r.ds, (float)kmax), 0.0f)) + 1;
+                kn = kn > k + 1 ? kn : k + 1;
+                if (kn > k + 1 && !tsdf_same_block(r, kn - 1, nx, ny, nz, bx, by, bz)) {
+                    kn = kn - 1;
+                    if (kn > k + 1 && !tsdf_same_block(r, kn - 1, nx, ny, nz, bx, by, bz)) kn = k + 1;
+                }
+                prev = NAN;
+                k = kn;
+                continue;
+            }
+        }
+        float c[8];
+        tsdf_corners(f, base, nx, ny, c);
+        cur = tsdf_trilinear(c, tx, ty, tz);
+        evaluated = evaluated + 1;
+        if (prev == prev && cur == cur && (prev < 0.0f) != (cur < 0.0f)) {
+            status = cur < 0.0f ? 1u : 2u;
+            break;
+        }
+        prev = cur;
+        k = k + 1;
+    }
+    const size_t plane = (size_t)p.h * p.w, pix = (size_t)view * plane + (size_t)y * p.w + x, pix3 = (size_t)view * 3 * plane + (size_t)y * p.w + x;
+    float depth = 0.0f, n0 = 0.0f, n1 = 0.0f, n2 = 0.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+    if (status == 1u) {
+        depth = (s_in + (float)(k - 1) * r.ds) + r.ds * (prev / (prev - cur));
+        float c[8];
+        if (p.normal || p.colours) {                  // (base, tx, ty, tz: sample k's, from the loop)
+            int cx, cy, cz;
+            float hx, hy, hz;
+            const int hit = tsdf_ray_cell(r, depth, nx, ny, nz, cx, cy, cz, hx, hy, hz);
+            tsdf_corners(f, hit, nx, ny, c);
+            bool known = true;
+            NR_PRAGMA_UNROLL
+            for (int j = 0; j < 8; ++j) known = known && c[j] == c[j];
+            if (known) { base = hit; tx = hx; ty = hy; tz = hz; }
+            else tsdf_corners(f, base, nx, ny, c);
+        }
+        if (p.normal) {
+            const float gx = tsdf_lerp(tsdf_lerp(c[1] - c[0], c[3] - c[2], ty), tsdf_lerp(c[5] - c[4], c[7] - c[6], ty), tz);
+            const float gy = tsdf_lerp(tsdf_lerp(c[2] - c[0], c[3] - c[1], tx), tsdf_lerp(c[6] - c[4], c[7] - c[5], tx), tz);
+            const float gz = tsdf_lerp(tsdf_lerp(c[4] - c[0], c[5] - c[1], tx), tsdf_lerp(c[6] - c[2], c[7] - c[3], tx), ty);
+            const float len2 = (gx * gx + gy * gy) + gz * gz;
+            if (len2 > 0.0f) { const float len = sqrtf(len2); n0 = gx / len; n1 = gy / len; n2 = gz / len; }
+        }
+        if (p.colours) {
+            c0 = c1 = c2 = 0.5f;
+            if (p.csum) {
+                const size_t vol = (size_t)nx * ny * nz;
+                tsdf_corners(p.cw, base, nx, ny, c);
+                const float den = tsdf_trilinear(c, tx, ty, tz);
+                if (den > 0.0f) {
+                    tsdf_corners(p.csum, base, nx, ny, c);
+                    c0 = tsdf_trilinear(c, tx, ty, tz) / den;
+                    tsdf_corners(p.csum + vol, base, nx, ny, c);
+                    c1 = tsdf_trilinear(c, tx, ty, tz) / den;
+                    tsdf_corners(p.csum + 2 * vol, base, nx, ny, c);
+                    c2 = tsdf_trilinear(c, tx, ty, tz) / den;
+                }
+            }
+        }
+    }
+    p.depth[pix] = depth;
+    p.status[pix] = (unsigned char)status;
+    if (p.normal) { p.normal[pix3] = n0; p.normal[pix3 + plane] = n1; p.normal[pix3 + 2 * plane] = n2; }
+    if (p.colours) { p.colours[pix3] = c0; p.colours[pix3 + plane] = c1; p.colours[pix3 + 2 * plane] = c2; }
+    if (p.evaluated) p.evaluated[pix] = evaluated;
 }
 
 }  // namespace nr

@@ -1140,6 +1140,104 @@ class RenderEngine:
         self._event_done(ev, 'surface_emit', flat.numel())
         return out
 
+    # ---- ray casting of a volume (neuray_amd/mesh.py) ----
+    def surface_blocks(self, cells, dims):
+        """One byte per block of 8 x 8 x 8 cells (neuray_surface_blocks): 1 where a cell of the block or within one cell of it is active ->
+        uint8 [bz,by,bx], b = ceil((n - 1) / 8).  cells: surface_cells' bytes."""
+        if self.variant != 'fp32':
+            raise NotImplementedError("neuray_amd: the mesh export lives in the fp32 library (variant=%r)" % (self.variant,))
+        nx, ny, nz = (int(d) for d in dims)
+        if not (torch.is_tensor(cells) and cells.dtype == torch.uint8 and tuple(cells.shape) == (nz - 1, ny - 1, nx - 1) and cells.is_contiguous()
+                and cells.device == self.device):
+            raise ValueError("neuray_amd: cells: uint8 %s on %s, contiguous" % ((nz - 1, ny - 1, nx - 1), self.device))
+        blocks = self.empty(*(max(-(-(d - 1) // _lib.TSDF_BLOCK), 0) for d in (nz, ny, nx)), dtype=torch.uint8)
+        a = _lib.NeuraySurfaceBlocksArgs(cells.data_ptr(), blocks.data_ptr(), nx, ny, nz, 0)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_surface_blocks(C.byref(a), self._stream()))
+        self._event_done(ev, 'surface_blocks', blocks.numel())
+        return blocks
+
+    def ray_table(self, poses, Ks):
+        """[n,12] float32 on the device: mesh.ray_table - M = R^T K^-1 row-major, then c = -R^T t, made on the host in float64 and rounded
+        once.  Cameras given as device tensors are read back for it (12 floats per view): prepare the table once and pass it as `rays`
+        where the call must not synchronise."""
+        from .mesh import ray_table
+        return torch.from_numpy(ray_table(poses, Ks)).to(self.device)
+
+    def tsdf_raycast(self, state_or_field, origin, voxel_size, dims, poses, Ks, h, w, step=0.5, depth_range=None, blocks=None,
+                     outputs=('depth', 'normal', 'colors', 'status'), min_weight=1.0, rays=None):
+        """A volume seen from cameras (include/neuray_hip.h, neuray_tsdf_raycast): per view and pixel the first zero crossing of the field
+        along the pixel's ray.  state_or_field: the field f [nz,ny,nx] (NaN = unknown; grey colours), or a volume's state dict - tsum / w,
+        from which f = tsum / w where w >= min_weight is made by one torch.where, or 'f' itself - with csum / cw for colours.  poses
+        [n,3,4], Ks [n,3,3]; step in voxels, 0 < step <= 0.95; depth_range [n,2] near, far or None: [0, inf); blocks: surface_blocks'
+        bytes or None (evaluate every sample).  -> dict of device tensors: depth [n,h,w], status [n,h,w] uint8 and, as `outputs` asks,
+        normal [n,3,h,w], colors [n,3,h,w], evaluated [n,h,w] int32.  rays: ray_table(poses, Ks) made earlier (poses and Ks are then
+        not looked at).  No host synchronisation with host cameras or a prepared table."""
+        if self.variant != 'fp32':
+            raise NotImplementedError("neuray_amd: the mesh export lives in the fp32 library (variant=%r)" % (self.variant,))
+        nx, ny, nz = (int(d) for d in dims)
+        unknown = set(outputs) - {'depth', 'normal', 'colors', 'status', 'evaluated'}
+        if unknown:
+            raise ValueError("neuray_amd: unknown raycast outputs %r" % (sorted(unknown),))
+        csum = cw = None
+        if isinstance(state_or_field, dict):
+            st = state_or_field
+            csum, cw = st.get('csum'), st.get('cw')
+            if st.get('f') is not None:
+                field = st['f']
+            else:
+                if not min_weight > 0:
+                    raise ValueError("neuray_amd: min_weight must be positive")
+                field = torch.where(st['w'] >= float(min_weight), st['tsum'] / st['w'], torch.full_like(st['w'], float('nan')))
+        else:
+            field = state_or_field
+        for name, t, shape in (('field', field, (nz, ny, nx)), ('csum', csum, (3, nz, ny, nx)), ('cw', cw, (nz, ny, nx))):
+            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()
+                                      and t.device == self.device):
+                raise ValueError("neuray_amd: %s: float32 %s on %s, contiguous" % (name, shape, self.device))
+        if (csum is None) != (cw is None):
+            raise ValueError("neuray_amd: csum and cw go together")
+        h, w = int(h), int(w)
+        if rays is None:
+            rays = self.ray_table(poses, Ks)
+        elif not (torch.is_tensor(rays) and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 12 and rays.is_contiguous()
+                  and rays.device == self.device):
+            raise ValueError("neuray_amd: rays: float32 [n,12] on %s, contiguous" % (self.device,))
+        n = rays.shape[0]
+        rng = None
+        if depth_range is not None:
+            if not (torch.is_tensor(depth_range) and depth_range.device.type == 'cuda'):          # (a device tensor is not read back: a view
+                r = np.asarray(depth_range.detach().cpu().numpy() if torch.is_tensor(depth_range) else depth_range, np.float32)      # with near > far is empty)
+                if r.shape != (n, 2) or not np.all((r[:, 0] >= 0) & (r[:, 0] <= r[:, 1])):
+                    raise ValueError("neuray_amd: depth_range [%d,2] with 0 <= near <= far" % n)
+                depth_range = torch.from_numpy(r)
+            rng = self._f32(depth_range)
+            if tuple(rng.shape) != (n, 2):
+                raise ValueError("neuray_amd: depth_range [%d,2]: %s" % (n, tuple(rng.shape)))
+        if blocks is not None:
+            want = tuple(-(-(d - 1) // _lib.TSDF_BLOCK) for d in (nz, ny, nx))
+            if not (torch.is_tensor(blocks) and blocks.dtype == torch.uint8 and tuple(blocks.shape) == want and blocks.is_contiguous()
+                    and blocks.device == self.device):
+                raise ValueError("neuray_amd: blocks: uint8 %s on %s, contiguous" % (want, self.device))
+        out = {'depth': self.empty(n, max(h, 0), max(w, 0)), 'status': self.empty(n, max(h, 0), max(w, 0), dtype=torch.uint8)}
+        if 'normal' in outputs:
+            out['normal'] = self.empty(n, 3, max(h, 0), max(w, 0))
+        if 'colors' in outputs:
+            out['colors'] = self.empty(n, 3, max(h, 0), max(w, 0))
+        if 'evaluated' in outputs:
+            out['evaluated'] = self.empty(n, max(h, 0), max(w, 0), dtype=torch.int32)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        a = _lib.NeurayTsdfRaycastArgs(field.data_ptr(), ptr(csum), ptr(cw), rays.data_ptr(), ptr(rng), ptr(blocks), out['depth'].data_ptr(),
+                                       ptr(out.get('normal')), ptr(out.get('colors')), out['status'].data_ptr(), ptr(out.get('evaluated')),
+                                       float(origin[0]), float(origin[1]), float(origin[2]), float(voxel_size), float(step), 0.0,
+                                       nx, ny, nz, n, h, w, 0, 0)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_tsdf_raycast(C.byref(a), self._stream()))
+        self._event_done(ev, 'tsdf_raycast', n * h * w)
+        return out
+
     def direct_render_rays_backward(self, alpha, colors, d_pixel, d_hit_prob=None):
         """Backward of direct_render's ray kernel: alpha [rn,dn] (logits), colors [rn,dn,3] (the SH colours), d_pixel [rn,3], d_hit_prob
         [rn,dn] or None -> (d_alpha [rn,dn], d_colors [rn,dn,3])"""

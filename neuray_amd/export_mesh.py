@@ -2,21 +2,29 @@
 
     python -m neuray_amd.export_mesh --database NAME --depth database|render [--cfg CFG --ckpt CKPT] --voxel V --out mesh.ply
                                      [--trunc T --min-weight 1 --no-filter --src 8 --tau-px 1 --tau-d 0.01 --min-views 2 --json out.json]
+                                     [--raycast DIR --step 0.5]
 
 fuses the depth maps of every view of a database - its own (`--depth database`), or the `render_depth_fine` of a renderer that renders each
 view from its nearest other views (`--depth render`, as neuray_amd.export_points) - into a truncated signed distance field of voxel size V
 (default: 256 lattice points on the longest side of the depths' bounding box) and writes its zero surface as a binary PLY with normals,
 colours and triangles.  The printed line carries the vertex count, the face count and the number of boundary edges (0: the surface is closed)
-and, for a procedural scene, the distance of the vertices to the true surface.
+and, for a procedural scene, the distance of the vertices to the true surface.  `--raycast DIR` casts the fused volume from every view's
+camera (mesh.TSDFVolume.raycast) and writes DIR/<view id>.npz with depth [h,w], normal [3,h,w], colour [3,h,w] and status
+[h,w]; for a procedural scene the line gains `raycast_depth`, for all views and for the held-out ones (every 8th, get_database_split's rule):
+the share of the true foreground pixels with a hit, the share of the hits that lie on true background, and the median and 95th percentile of
+|depth - true depth| over the pixels that have both.
 
     python -m neuray_amd.export_mesh --time
 
 measures the kernels on the MI355X at 48 views of 800 x 800 of procedural scene 1 and a 256^3 volume over the scene's ball - the integration
 of all 48 views (one launch) and the extraction (surface_cells + the two prefix sums + surface_emit, with its one read-back) - with device
 events, the median of 20 after warm-up, next to an eager PyTorch composition of the same formulas in the same process, and reports the share of
-the HBM peak that the compulsory traffic amounts to.  One JSON line."""
+the HBM peak that the compulsory traffic amounts to - and the ray casting of the fused volume from the same 48 cameras at 800 x 800: the
+kernel with block skipping and without, the preparation (field, cell bytes, block bytes), an eager PyTorch composition of the same
+fixed-step march without skipping, and the field samples per second from the `evaluated` output.  One JSON line."""
 import argparse
 import json
+import os
 
 import numpy as np
 import torch
@@ -48,10 +56,42 @@ def export(args):
            'on': 'hip' if vol.engine is not None else 'numpy',
            'settings': {'filter': not args.no_filter, 'src': args.src, 'tau_px': args.tau_px, 'tau_d': args.tau_d, 'min_views': args.min_views,
                         'min_weight': args.min_weight}}
+    if args.raycast:
+        res['raycast'] = args.raycast
+        res.update(raycast_export(args, db, ids, maps, vol))
     if isinstance(db, procedural.ProceduralDatabase) and res['vertices']:
         dist = geometry.surface_distance(db.scene, out['vertices'])
         res['surface_distance'] = {'mean': float(dist.mean()), 'median': float(np.median(dist)), 'p95': float(np.percentile(dist, 95)),
                                    'max': float(dist.max())}
+    return res
+
+
+def depth_scores(cast, status, true):
+    """ray-cast depth against the true depth over views [m,h,w] -> the `raycast_depth` figures"""
+    hit, fg = status == 1, true > 0
+    both = hit & fg
+    err = np.abs(cast.astype(np.float64) - true)[both]
+    return {'views': int(cast.shape[0]), 'foreground_hit_share': float(both.sum() / max(fg.sum(), 1)),
+            'hits_on_background_share': float((hit & ~fg).sum() / max(hit.sum(), 1)),
+            'median': float(np.median(err)) if err.size else None, 'p95': float(np.percentile(err, 95)) if err.size else None}
+
+
+def raycast_export(args, db, ids, maps, vol):
+    """casts `vol` from the cameras of `maps`, writes the .npz files and scores the depth against the TRUE depth of a procedural database -
+    the database's own maps, whatever depth was fused (`maps['depth']` is the renderer's with --depth render)"""
+    n, h, w = maps['depth'].shape
+    out = {k: geometry._host(v) for k, v in vol.raycast(maps['poses'], maps['Ks'], h, w, args.min_weight, args.step).items()}
+    os.makedirs(args.raycast, exist_ok=True)
+    for i, view_id in enumerate(ids):
+        np.savez(os.path.join(args.raycast, '%s.npz' % view_id), depth=out['depth'][i], normal=out['normal'][i], colour=out['colors'][i],
+                 status=out['status'][i])
+    res = {'raycast_step': args.step, 'raycast_hits': int((out['status'] == 1).sum())}
+    if isinstance(db, procedural.ProceduralDatabase):
+        held = np.array([v in set(_database.get_database_split(db, 'val_all')[1]) for v in ids])
+        true = maps['depth'] if args.depth == 'database' else geometry.database_depth_maps(db, ids)['depth']
+        res['raycast_depth'] = {'all': depth_scores(out['depth'], out['status'], true)}
+        if held.any():
+            res['raycast_depth']['held_out'] = depth_scores(out['depth'][held], out['status'][held], true[held])
     return res
 
 
@@ -115,6 +155,100 @@ def eager_cells(tsum, w, min_weight):
     return cells
 
 
+def eager_raycast(field, rays, origin, vs, dims, h, w, step):
+    """mesh.raycast_numpy's fixed-step march in eager PyTorch on the device, every sample evaluated, depth and status only (no normals or
+    colours: less work than the kernel does) -> (depth [n,h,w], status [n,h,w] uint8).  One read-back: the longest ray's sample count."""
+    nx, ny, nz = dims
+    dev = field.device
+    n = rays.shape[0]
+    F = field.reshape(-1)
+    ys, xs = torch.meshgrid(torch.arange(h, device=dev, dtype=torch.float32), torch.arange(w, device=dev, dtype=torch.float32), indexing='ij')
+    M = rays[:, :, None, None]
+    d = [(M[:, 3 * a] * xs + M[:, 3 * a + 1] * ys) + M[:, 3 * a + 2] for a in range(3)]
+    g0 = [((M[:, 9 + a] - origin[a]) / vs).expand(n, h, w) for a in range(3)]
+    gd = [d[a] / vs for a in range(3)]
+    s_in, s_out = torch.zeros(n, h, w, device=dev), torch.full((n, h, w), float('inf'), device=dev)
+    ok = torch.ones(n, h, w, dtype=torch.bool, device=dev)
+    for a in range(3):
+        hi = float(dims[a] - 1)
+        zero = gd[a] == 0
+        t1, t2 = (0.0 - g0[a]) / gd[a], (hi - g0[a]) / gd[a]
+        s_in = torch.where(zero, s_in, torch.maximum(s_in, torch.minimum(t1, t2)))
+        s_out = torch.where(zero, s_out, torch.minimum(s_out, torch.maximum(t1, t2)))
+        ok = ok & ~(zero & ((g0[a] < 0) | (g0[a] > hi)))
+    ds = (step * vs) / torch.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+    ok = ok & (s_in <= s_out) & (ds > 0)
+    kmax = torch.where(ok, torch.floor((s_out - s_in) / ds), torch.full_like(ds, -1.0))
+    prev = torch.full((n, h, w), float('nan'), device=dev)
+    depth, status = torch.zeros(n, h, w, device=dev), torch.zeros(n, h, w, dtype=torch.uint8, device=dev)
+    done = ~ok
+    for k in range(int(kmax.max()) + 1):
+        s = s_in + float(k) * ds
+        idx, t = 0, []
+        for a, (stride, cells) in enumerate(((1, nx - 1), (nx, ny - 1), (nx * ny, nz - 1))):
+            g = g0[a] + s * gd[a]
+            c = torch.clamp(torch.floor(torch.nan_to_num(g)), 0, cells - 1)
+            t.append(g - c)
+            idx = idx + c.long() * stride
+        c = [F[idx + ((j >> 2) * ny + ((j >> 1) & 1)) * nx + (j & 1)] for j in range(8)]
+        a4 = [c[2 * j] + t[0] * (c[2 * j + 1] - c[2 * j]) for j in range(4)]
+        b0, b1 = a4[0] + t[1] * (a4[1] - a4[0]), a4[2] + t[1] * (a4[3] - a4[2])
+        cur = b0 + t[2] * (b1 - b0)
+        cross = ~done & (kmax >= k) & (prev == prev) & (cur == cur) & ((prev < 0) != (cur < 0))
+        front = cross & (cur < 0)
+        depth = torch.where(front, (s_in + float(k - 1) * ds) + ds * (prev / (prev - cur)), depth)
+        status = torch.where(cross, torch.where(front, 1, 2).to(torch.uint8), status)
+        done = done | cross
+        prev = cur
+    return depth, status
+
+
+def timing_raycast(eng, vol, t_poses, t_Ks, h, w, eager_reps=2, step=0.5):
+    """the raycast leg of --time on the fused volume: the kernel launch with and without block skipping (field, blocks and ray table
+    prepared once), the preparation, TSDFVolume.raycast as a whole from host cameras, and the eager march"""
+    state, dims, n = vol.state(), vol.dims, t_poses.shape[0]
+    prep, last = {}, {}
+
+    def run_prepare():
+        prep['f'] = vol.field()
+        prep['blocks'] = eng.surface_blocks(eng.surface_cells(state, dims), dims)
+    ms_prep = _median_ms(run_prepare)
+    src = {'f': prep['f'], 'csum': state.get('csum'), 'cw': state.get('cw')}
+    poses, Ks = t_poses.cpu().numpy(), t_Ks.cpu().numpy()
+    rays = eng.ray_table(poses, Ks)
+    outs = ('depth', 'normal', 'colors', 'status', 'evaluated')
+
+    def run_skip():                                   # (the launch alone: field, blocks and ray table prepared)
+        last['skip'] = eng.tsdf_raycast(src, vol.origin, vol.voxel_size, dims, None, None, h, w, step, None, prep['blocks'], outs, rays=rays)
+
+    def run_all():
+        last['all'] = eng.tsdf_raycast(src, vol.origin, vol.voxel_size, dims, None, None, h, w, step, None, None, outs, rays=rays)
+
+    def run_whole():                                  # (everything: field, cell and block bytes, the ray table from host cameras, the launch)
+        last['whole'] = vol.raycast(poses, Ks, h, w, step=step)
+    ms_skip, ms_all, ms_whole = _median_ms(run_skip), _median_ms(run_all), _median_ms(run_whole)
+
+    def run_eager():
+        last['eager'] = eager_raycast(prep['f'], rays, vol.origin, vol.voxel_size, dims, h, w, step)
+    ms_eager = _median_ms(run_eager, reps=eager_reps, warmup=1)
+    torch.cuda.synchronize(eng.device)
+    a, b = last['skip'], last['all']
+    ev_skip, ev_all = int(a['evaluated'].sum()), int(b['evaluated'].sum())
+    same = all(torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)) for k in ('depth', 'normal', 'colors', 'status'))
+    hits = b['status'] == 1
+    e_depth, e_status = last['eager']
+    both = hits & (e_status == 1)
+    return {'raycast_48_views_ms' if n == 48 else 'raycast_ms': ms_skip, 'raycast_no_skip_ms': ms_all, 'raycast_prepare_ms': ms_prep,
+            'raycast_with_prepare_ms': ms_whole, 'eager_raycast_ms': ms_eager, 'raycast_step': step, 'raycast_hits': int(hits.sum()),
+            'raycast_evaluated': ev_skip, 'raycast_evaluated_no_skip': ev_all, 'raycast_flagged_blocks': int(prep['blocks'].sum()),
+            'raycast_blocks': int(prep['blocks'].numel()), 'raycast_evaluations_per_s': ev_skip / (ms_skip * 1e-3),
+            'raycast_evaluations_per_s_no_skip': ev_all / (ms_all * 1e-3), 'raycast_skip_bitwise_equal': bool(same),
+            'eager_raycast_status_agreement': float((e_status == b['status']).float().mean()),
+            'eager_raycast_depth_within_1e-5': float(((e_depth - b['depth'])[both].abs() <= 1e-5).float().mean()) if bool(both.any()) else None,
+            'eager_raycast_depth_max_diff': float((e_depth - b['depth'])[both].abs().max()) if bool(both.any()) else None,
+            'eager_raycast_reps': eager_reps}
+
+
 def timing(n=48, size=800, points=256, eager_reps=3):
     from .engine import host_inverse
     dev = torch.device('cuda:0')
@@ -174,7 +308,8 @@ def timing(n=48, size=800, points=256, eager_reps=3):
     w_agree = float((eager['w'] == state['w']).float().mean())
     cells_agree = float((eager['cells'] == last['cells']).float().mean())
     dist = geometry.surface_distance(procedural.make_scene(1), last['vertices'])
-    return {'views': n, 'h': h, 'w': w, 'dims': list(dims), 'voxel_size': vs, 'trunc': trunc, 'vertices': m, 'faces': k,
+    cast = timing_raycast(eng, vol, t_poses, t_Ks, h, w)
+    return {**cast, 'views': n, 'h': h, 'w': w, 'dims': list(dims), 'voxel_size': vs, 'trunc': trunc, 'vertices': m, 'faces': k,
             'boundary_edges': mesh.boundary_edges(last['faces']),
             'surface_distance': {'median': float(np.median(dist)), 'p95': float(np.percentile(dist, 95))},
             'integrate_48_views_ms' if n == 48 else 'integrate_ms': ms_i, 'state_zero_ms': ms_zero, 'extract_ms': ms_e, 'surface_cells_ms': ms_cells,
@@ -199,6 +334,8 @@ def main(argv=None):
     ap.add_argument('--tau-d', type=float, default=geometry.DEFAULTS['tau_d'])
     ap.add_argument('--min-views', type=int, default=geometry.DEFAULTS['min_views'])
     ap.add_argument('--json', type=str, default=None, help='write the result line here as well')
+    ap.add_argument('--raycast', type=str, default=None, help='cast the fused volume from every view and write DIR/<view id>.npz')
+    ap.add_argument('--step', type=float, default=0.5, help='sample spacing of --raycast in voxels, in (0, 0.95]')
     ap.add_argument('--time', action='store_true')
     args = ap.parse_args(argv)
     if args.time:
@@ -208,6 +345,8 @@ def main(argv=None):
             ap.error('--database is required')
         if (args.voxel is not None and not args.voxel > 0) or (args.trunc is not None and not args.trunc > 0) or not args.min_weight > 0:
             ap.error('--voxel, --trunc and --min-weight must be positive')
+        if not 0 < args.step <= mesh.MAX_STEP:
+            ap.error('--step must be in (0, %g]' % mesh.MAX_STEP)
         if not 1 <= args.src <= geometry.MAX_SRC:
             ap.error('--src must be in 1 .. %d' % geometry.MAX_SRC)
         res = export(args)

@@ -21,7 +21,36 @@ An active cell's vertex is origin + (cell + m) * vs, m the mean of the crossing 
 in `inside` (the four x-edges, then y, then z, each with the other two offsets - in ascending axis order - running 00, 10, 01, 11); its normal
 the normalised sums of the forward differences of f over the four edges per axis (towards free space); its colour sum Csum / sum Cw over the
 corners in corner order (x fastest), 0.5 grey where that is 0 / 0.  A quad is the four cells' vertices in the order above where the edge's low
-end is inside, reversed otherwise; its triangles are (v0, v1, v2) and (v0, v2, v3); faces are ordered by owner cell, then axis."""
+end is inside, reversed otherwise; its triangles are (v0, v1, v2) and (v0, v2, v3); faces are ordered by owner cell, then axis.
+
+Ray casting of a volume: per view and pixel the first zero crossing of the field along the pixel's ray (DESIGN.md 4.22;
+csrc/nr_kernels_tsdf.h evaluates the same operations in fp32, `raycast_numpy` restates them in float64 or float32).
+
+  field: f = Tsum / W in float32, NaN ("unknown") where W < min_weight (`field_numpy`).  A cell is valid where none of its 8 corners is unknown.
+  ray of pixel (x, y) of view i (pixel centres at integers): the 12 floats M = R^T K^-1 (row-major) and c = -R^T t, made in float64 and
+    rounded to float32 (`ray_table`); d[a] = (M[a][0] x + M[a][1] y) + M[a][2]; the point at z-depth s is c + s d, so s is z-depth; in
+    lattice units g[a](s) = g0[a] + s gd[a] with g0[a] = (c[a] - origin[a]) / vs and gd[a] = d[a] / vs.
+  interval: [s_in, s_out] starts as [near, far] (depth_range [n,2], default [0, inf)); per axis a with hi = n[a] - 1: if gd[a] == 0 the ray
+    is empty where g0[a] < 0 or g0[a] > hi, else t1 = (0 - g0[a]) / gd[a], t2 = (hi - g0[a]) / gd[a], s_in = max(s_in, min(t1, t2)), s_out =
+    min(s_out, max(t1, t2)).  Empty unless s_in <= s_out: status 0.
+  samples: ds = (step vs) / sqrt((d0 d0 + d1 d1) + d2 d2), step in voxels, 0 < step <= 0.95 (a ray without 0 < ds < inf is empty); s_k = s_in +
+    k ds for k = 0 .. floor(min((s_out - s_in) / ds, 2^22)).
+  value at s: cell[a] = clamp(floor(g[a]), 0, n[a] - 2), t[a] = g[a] - cell[a]; with the corners c_j, j = dz 4 + dy 2 + dx, and lerp(p, q,
+    t) = p + t (q - p): along x first, a_0..3 = lerp(c_0, c_1), lerp(c_2, c_3), lerp(c_4, c_5), lerp(c_6, c_7) at t[0]; then y, b_0 =
+    lerp(a_0, a_1), b_1 = lerp(a_2, a_3) at t[1]; then z, lerp(b_0, b_1) at t[2].  Unknown (NaN) if any corner is.
+  first crossing: the first k whose samples k - 1 and k are both known (and both evaluated) with (f_{k-1} < 0) != (f_k < 0) - inside is f <
+    0, the extraction's definition.  f_k < 0: status 1 (hit), depth = s_{k-1} + ds (f_{k-1} / (f_{k-1} - f_k)); otherwise status 2 (the
+    surface seen from behind), depth 0.  The ray ends there.  No crossing: status 0, depth 0.
+  at a hit: the cell and t of g(depth) where that cell is valid, else those of sample k.  Normal: the gradient of the trilinear interpolant
+    there - per axis the four corner differences along it (the other two offsets, in ascending axis order, running 00, 10, 01, 11), lerped
+    over the lower, then the higher of the other two axes - divided by its length (towards free space, surface_emit's sign; zero where the
+    length is zero).  Colour: the trilinear combination of Csum[c] over that of Cw; 0.5 grey where that denominator is not positive or the
+    volume has no colour.  Pixels without a hit have zero normals and colours.
+  block skipping: `blocks` (`blocks_numpy`) holds one byte per block of 8 x 8 x 8 cells, non-zero where a cell of the block or within one
+    cell of it is active.  A sample whose cell lies in an unflagged block is not evaluated and counts as unknown; k then moves to kn = max(k
+    + 1, floor(clamp((s_exit - s_in) / ds, 0, kmax)) + 1), s_exit the smallest over the axes with gd[a] != 0 of ((gd[a] > 0 ? 8 (b[a] + 1) :
+    8 b[a]) - g0[a]) / gd[a], provided the cell of sample kn - 1 lies in the same block b; if it does not, kn - 1 is tried the same way, and k
+    + 1 is taken if that fails too.  No output but `evaluated` (the number of field samples evaluated) depends on `blocks`."""
 import numpy as np
 import torch
 
@@ -227,6 +256,227 @@ def boundary_edges(faces):
     return int((counts == 1).sum())
 
 
+# ---- ray casting --------------------------------------------------------------------------------------------------------
+BLOCK = 8
+RAYCAST_MAX_K = 1 << 22
+MAX_STEP = 0.95
+
+
+def field_numpy(tsum, w, min_weight=1.0):
+    """f = Tsum / W as float32 [nz,ny,nx], NaN where W < min_weight"""
+    if not min_weight > 0:
+        raise ValueError("neuray_amd.mesh: min_weight must be positive")
+    tsum, w = np.asarray(tsum, np.float32), np.asarray(w, np.float32)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(w >= np.float32(min_weight), tsum / w, np.float32('nan')).astype(np.float32)
+
+
+def ray_table(poses, Ks):
+    """[n,12] float32: M = R^T K^-1 row-major, then c = -R^T t; float64 arithmetic on the float32 cameras, rounded once"""
+    P = np.asarray(_geo._host(poses), np.float32).reshape(-1, 3, 4).astype(np.float64)
+    K = np.asarray(_geo._host(Ks), np.float32).reshape(-1, 3, 3).astype(np.float64)
+    if P.shape[0] != K.shape[0]:
+        raise ValueError("neuray_amd.mesh: %d poses, %d Ks" % (P.shape[0], K.shape[0]))
+    Rt = P[:, :, :3].transpose(0, 2, 1)
+    return np.concatenate([(Rt @ np.linalg.inv(K)).reshape(-1, 9), -(Rt @ P[:, :, 3:])[:, :, 0]], 1).astype(np.float32)
+
+
+def blocks_numpy(cells):
+    """cell bytes [nz-1,ny-1,nx-1] -> uint8 [bz,by,bx], b = ceil((n - 1) / 8): 1 where a cell of the block or within one cell of it is active"""
+    active = (np.asarray(cells) & 1) > 0
+    if active.ndim != 3 or min(active.shape) < 1:
+        raise ValueError("neuray_amd.mesh: cells %r ([nz-1,ny-1,nx-1])" % (active.shape,))
+    grown = np.zeros(tuple(s + 2 for s in active.shape), bool)
+    for dz in range(3):
+        for dy in range(3):
+            for dx in range(3):
+                grown[dz:dz + active.shape[0], dy:dy + active.shape[1], dx:dx + active.shape[2]] |= active
+    grown = grown[1:-1, 1:-1, 1:-1]
+    nb = tuple(-(-s // BLOCK) for s in active.shape)
+    padded = np.zeros(tuple(b * BLOCK for b in nb), bool)
+    padded[:active.shape[0], :active.shape[1], :active.shape[2]] = grown
+    return padded.reshape(nb[0], BLOCK, nb[1], BLOCK, nb[2], BLOCK).any((1, 3, 5)).astype(np.uint8)
+
+
+def _check_raycast(shape, voxel_size, h, w, step, n, depth_range, blocks):
+    nz, ny, nx = shape
+    _check_volume((nx, ny, nz), voxel_size, 1.0)
+    if h < 1 or w < 1:
+        raise ValueError("neuray_amd.mesh: image size h=%d w=%d must be positive" % (h, w))
+    if not 0 < step <= MAX_STEP:
+        raise ValueError("neuray_amd.mesh: step=%r outside (0, %g] voxels" % (step, MAX_STEP))
+    if depth_range is not None:
+        depth_range = np.asarray(_geo._host(depth_range), np.float32)
+        if depth_range.shape != (n, 2) or not np.all((depth_range[:, 0] >= 0) & (depth_range[:, 0] <= depth_range[:, 1])):
+            raise ValueError("neuray_amd.mesh: depth_range [%d,2] with 0 <= near <= far" % n)
+    if blocks is not None:
+        blocks = np.asarray(blocks)
+        want = tuple(-(-(s - 1) // BLOCK) for s in shape)
+        if blocks.shape != want:
+            raise ValueError("neuray_amd.mesh: blocks %r for a volume of %r cells (%r)" % (blocks.shape, tuple(s - 1 for s in shape), want))
+    return depth_range, blocks
+
+
+def _lerp(a, b, t):
+    return a + t * (b - a)
+
+
+def _trilinear(c, t):
+    a = [_lerp(c[2 * j], c[2 * j + 1], t[0]) for j in range(4)]
+    return _lerp(_lerp(a[0], a[1], t[1]), _lerp(a[2], a[3], t[1]), t[2])
+
+
+def raycast_numpy(field, csum, cw, origin, voxel_size, poses, Ks, h, w, step=0.5, depth_range=None, dtype=np.float64, blocks=None,
+                  details=False):
+    """The reference of the ray caster (the module docstring states the operations), vectorised over the pixels.  field [nz,ny,nx] float32 (`field_numpy`), csum
+    [3,nz,ny,nx] / cw [nz,ny,nx] or None -> dict(depth [n,h,w] dtype, normal [n,3,h,w], colors [n,3,h,w], status [n,h,w] uint8, evaluated
+    [n,h,w] int32) and, with details, per pixel float64: 'min_abs_f' (the smallest |f| of a known evaluated sample), 'end' (the distance of
+    (s_out - s_in) / ds to an integer), 'block_face' (the smallest distance, in voxels, of a visited sample to a face between two blocks), 'cell_face'
+    (that of the hit point to a cell face); inf where there is none."""
+    T = np.dtype(dtype).type
+    field = np.asarray(field, np.float32)
+    if field.ndim != 3:
+        raise ValueError("neuray_amd.mesh: field %r ([nz,ny,nx])" % (field.shape,))
+    nz, ny, nx = field.shape
+    rays = ray_table(poses, Ks).astype(T)
+    n = rays.shape[0]
+    h, w = int(h), int(w)
+    depth_range, blocks = _check_raycast(field.shape, voxel_size, h, w, step, n, depth_range, blocks)
+    dims = (nx, ny, nz)
+    F = field.astype(T).reshape(-1)
+    o, vs, st = [T(np.float32(c)) for c in origin], T(np.float32(voxel_size)), T(np.float32(step))
+    view, py, px = [a.reshape(-1) for a in np.meshgrid(np.arange(n), np.arange(h), np.arange(w), indexing='ij')]
+    R = view.shape[0]
+    x, y = px.astype(T), py.astype(T)
+    cam = rays[view]
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        d = [(cam[:, 3 * a] * x + cam[:, 3 * a + 1] * y) + cam[:, 3 * a + 2] for a in range(3)]
+        g0 = [(cam[:, 9 + a] - o[a]) / vs for a in range(3)]
+        gd = [d[a] / vs for a in range(3)]
+        if depth_range is None:
+            s_in, s_out = np.zeros(R, T), np.full(R, T(np.inf))
+        else:
+            s_in, s_out = depth_range.astype(T)[view, 0], depth_range.astype(T)[view, 1]
+        ok = np.ones(R, bool)
+        for a in range(3):
+            hi = T(dims[a] - 1)
+            zero = gd[a] == 0
+            t1, t2 = (T(0) - g0[a]) / gd[a], (hi - g0[a]) / gd[a]
+            s_in = np.where(zero, s_in, np.maximum(s_in, np.minimum(t1, t2)))
+            s_out = np.where(zero, s_out, np.minimum(s_out, np.maximum(t1, t2)))
+            ok &= ~(zero & ((g0[a] < 0) | (g0[a] > hi)))
+        ds = (st * vs) / np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+        ok &= (s_in <= s_out) & (ds > 0) & (ds < np.inf)
+        q_end = (s_out - s_in) / ds
+        kmax = np.where(ok, np.floor(np.minimum(np.where(ok, q_end, 0), T(RAYCAST_MAX_K))), -1).astype(np.int64)
+
+        def cell_of(idx, s):
+            """(cell [3] int64, t [3], g [3]) of the points at z-depth s of the rays idx"""
+            g = [g0[a][idx] + s * gd[a][idx] for a in range(3)]
+            cell = [np.clip(np.floor(g[a]), 0, dims[a] - 2).astype(np.int64) for a in range(3)]
+            return cell, [g[a] - cell[a].astype(T) for a in range(3)], g
+
+        def corners(arr, cell):
+            base = (cell[2] * ny + cell[1]) * nx + cell[0]
+            return [arr[base + ((j >> 2) * ny + ((j >> 1) & 1)) * nx + (j & 1)] for j in range(8)]
+
+        def block_of(cell):
+            return [cell[a] >> 3 for a in range(3)]
+
+        nb = tuple(-(-(dims[a] - 1) // BLOCK) for a in range(3))
+        flags = None if blocks is None else (blocks.reshape(-1) != 0)
+        k = np.zeros(R, np.int64)
+        prev = np.full(R, T(np.nan))
+        status = np.zeros(R, np.uint8)
+        evaluated = np.zeros(R, np.int32)
+        f_lo, f_hi = np.zeros(R, T), np.zeros(R, T)
+        det = {key: np.full(R, np.inf) for key in ('min_abs_f', 'block_face', 'cell_face')} if details else None
+        live = np.flatnonzero(k <= kmax)
+        while live.size:
+            s = s_in[live] + k[live].astype(T) * ds[live]
+            cell, t, g = cell_of(live, s)
+            if details:
+                for a in range(3):                           # the faces between two blocks: 8 j for 1 <= j <= (n - 2) // 8
+                    ga = g[a].astype(np.float64)
+                    j = np.round(ga / BLOCK)
+                    face = np.where((j >= 1) & (j <= (dims[a] - 2) // BLOCK), np.abs(ga - j * BLOCK), np.inf)
+                    det['block_face'][live] = np.minimum(det['block_face'][live], face)
+            skip = np.zeros(live.size, bool)
+            if flags is not None:
+                b = block_of(cell)
+                skip = ~flags[(b[2] * nb[1] + b[1]) * nb[0] + b[0]]
+                if skip.any():
+                    idx = live[skip]
+                    bs, kk = [b[a][skip] for a in range(3)], k[idx]
+                    s_exit = None
+                    for a in range(3):
+                        face = np.where(gd[a][idx] > 0, (bs[a] + 1) * BLOCK, bs[a] * BLOCK).astype(T)
+                        e = np.where(gd[a][idx] == 0, T(np.inf), (face - g0[a][idx]) / gd[a][idx])
+                        s_exit = e if s_exit is None else np.minimum(s_exit, e)
+                    kn = np.floor(np.maximum(np.minimum((s_exit - s_in[idx]) / ds[idx], kmax[idx].astype(T)), T(0))).astype(np.int64) + 1
+                    kn = np.maximum(kn, kk + 1)
+
+                    def same(kq):
+                        bq = block_of(cell_of(idx, s_in[idx] + kq.astype(T) * ds[idx])[0])
+                        return (bq[0] == bs[0]) & (bq[1] == bs[1]) & (bq[2] == bs[2])
+                    bad = (kn > kk + 1) & ~same(kn - 1)
+                    kn = np.where(bad, kn - 1, kn)
+                    bad = bad & (kn > kk + 1) & ~same(kn - 1)
+                    kn = np.where(bad, kk + 1, kn)
+                    prev[idx] = T(np.nan)
+                    k[idx] = kn
+            ev = live[~skip]
+            cur = _trilinear(corners(F, [c[~skip] for c in cell]), [a[~skip] for a in t])
+            evaluated[ev] += 1
+            if details:
+                det['min_abs_f'][ev] = np.fmin(det['min_abs_f'][ev], np.abs(cur).astype(np.float64))
+            cross = (prev[ev] == prev[ev]) & (cur == cur) & ((prev[ev] < 0) != (cur < 0))
+            hit = ev[cross]
+            status[hit] = np.where(cur[cross] < 0, 1, 2)
+            f_lo[hit], f_hi[hit] = prev[hit], cur[cross]
+            kmax[hit] = -1                                   # the ray ends there (k stays at the crossing's)
+            go = ev[~cross]
+            prev[go] = cur[~cross]
+            k[go] += 1
+            live = live[k[live] <= kmax[live]]
+        hit = np.flatnonzero(status == 1)
+        depth = np.zeros(R, T)
+        depth[hit] = (s_in[hit] + (k[hit] - 1).astype(T) * ds[hit]) + ds[hit] * (f_lo[hit] / (f_lo[hit] - f_hi[hit]))
+        cell, t, g = cell_of(hit, depth[hit])
+        c = corners(F, cell)
+        known = np.ones(hit.size, bool)
+        for j in range(8):
+            known &= c[j] == c[j]
+        cell_k, t_k, _ = cell_of(hit, s_in[hit] + k[hit].astype(T) * ds[hit])
+        cell = [np.where(known, cell[a], cell_k[a]) for a in range(3)]
+        t = [np.where(known, t[a], t_k[a]) for a in range(3)]
+        c = corners(F, cell)
+        if details:
+            det['cell_face'][hit] = np.min([np.abs(g[a].astype(np.float64) - np.round(g[a].astype(np.float64))) for a in range(3)], 0)
+        grad = [_lerp(_lerp(c[1] - c[0], c[3] - c[2], t[1]), _lerp(c[5] - c[4], c[7] - c[6], t[1]), t[2]),
+                _lerp(_lerp(c[2] - c[0], c[3] - c[1], t[0]), _lerp(c[6] - c[4], c[7] - c[5], t[0]), t[2]),
+                _lerp(_lerp(c[4] - c[0], c[5] - c[1], t[0]), _lerp(c[6] - c[2], c[7] - c[3], t[0]), t[1])]
+        len2 = (grad[0] * grad[0] + grad[1] * grad[1]) + grad[2] * grad[2]
+        ln = np.sqrt(len2)
+        normal, colors = np.zeros((R, 3), T), np.zeros((R, 3), T)
+        colors[hit] = T(0.5)
+        for a in range(3):
+            normal[hit, a] = np.where(len2 > 0, grad[a] / ln, T(0))
+        if csum is not None:
+            den = _trilinear(corners(np.asarray(cw, np.float32).astype(T).reshape(-1), cell), t)
+            for a in range(3):
+                num = _trilinear(corners(np.asarray(csum[a], np.float32).astype(T).reshape(-1), cell), t)
+                colors[hit, a] = np.where(den > 0, num / den, T(0.5))
+    out = {'depth': depth.reshape(n, h, w), 'normal': normal.reshape(n, h, w, 3).transpose(0, 3, 1, 2).copy(),
+           'colors': colors.reshape(n, h, w, 3).transpose(0, 3, 1, 2).copy(), 'status': status.reshape(n, h, w),
+           'evaluated': evaluated.reshape(n, h, w)}
+    if details:
+        with np.errstate(invalid='ignore'):
+            det['end'] = np.where(ok, np.abs(q_end.astype(np.float64) - np.round(q_end.astype(np.float64))), np.inf)
+        out.update({key: v.reshape(n, h, w) for key, v in det.items()})
+    return out
+
+
 # ---- the public surface --------------------------------------------------------------------------------------------------------------
 class TSDFVolume:
     """A truncated signed distance field on a regular lattice: origin (3,), voxel_size, dims (nx, ny, nz); trunc defaults to 3 voxels.
@@ -285,6 +535,47 @@ class TSDFVolume:
             return self.engine.surface_emit(s, self.origin, self.voxel_size, self.dims, cells)
         ref = surface_nets_numpy(s['tsum'], s['w'], s.get('csum'), s.get('cw'), self.origin, self.voxel_size, min_weight, np.float32)
         return {k: ref[k] for k in ('vertices', 'faces', 'colors', 'normals')}
+
+    def field(self, min_weight=1):
+        """f = Tsum / W [nz,ny,nx] float32, NaN where W < min_weight: the ray caster's field (one elementwise pass)"""
+        if not min_weight > 0:
+            raise ValueError("neuray_amd.mesh: min_weight must be positive")
+        s = self._state
+        if self.engine is not None:
+            return torch.where(s['w'] >= float(min_weight), s['tsum'] / s['w'], torch.full_like(s['w'], float('nan')))
+        return field_numpy(s['tsum'], s['w'], min_weight)
+
+    def raycast(self, poses, Ks, h, w, min_weight=1, step=0.5, depth_range=None, skip=True):
+        """The volume seen from the cameras poses [n,3,4], Ks [n,3,3] at h x w pixels -> dict(depth [n,h,w] float32 z-depth, 0 = none;
+        normal [n,3,h,w] unit, towards free space; colors [n,3,h,w] in [0,1]; status [n,h,w] uint8: 0 nothing, 1 hit, 2 the surface seen
+        from behind; evaluated [n,h,w] int32).  step: the sample spacing in voxels, 0 < step <= 0.95; depth_range [n,2]: near, far per view
+        (default [0, inf)); skip: skip the blocks of 8 x 8 x 8 cells away from the surface (changes no bit of the other outputs).  Device
+        tensors where the volume lives on the device (no host synchronisation with host cameras), the float32 reference otherwise."""
+        f = self.field(min_weight)
+        s = self._state
+        nx, ny, nz = self.dims
+        n = int(np.asarray(poses).reshape(-1, 3, 4).shape[0]) if not torch.is_tensor(poses) else int(poses.reshape(-1, 3, 4).shape[0])
+        _check_raycast((nz, ny, nx), self.voxel_size, int(h), int(w), step, n, None if torch.is_tensor(depth_range) else depth_range, None)
+        if self.engine is not None:
+            blocks = self.engine.surface_blocks(self.engine.surface_cells(s, self.dims, min_weight), self.dims) if skip else None
+            state = {'f': f, 'csum': s.get('csum'), 'cw': s.get('cw')}
+            return self.engine.tsdf_raycast(state, self.origin, self.voxel_size, self.dims, poses, Ks, h, w, step, depth_range, blocks,
+                                            ('depth', 'normal', 'colors', 'status', 'evaluated'))
+        blocks = blocks_numpy(cells_numpy(s['tsum'], s['w'], min_weight, np.float32)[0]) if skip else None
+        return raycast_numpy(f, s.get('csum'), s.get('cw'), self.origin, self.voxel_size, poses, Ks, h, w, step, depth_range, np.float32, blocks)
+
+
+def raycast_views(volume, database, ids, min_weight=1, step=0.5):
+    """The volume seen from the database's views `ids` -> geometry.database_depth_maps' dictionary with
+    the ray-cast depth as an imgs_info has it: dict(depth [n,1,h,w], imgs [n,3,h,w] (the ray-cast colours), poses [n,3,4], Ks [n,3,3]) as
+    float32 numpy arrays, and normal [n,3,h,w], status [n,h,w]: what filter_depth, fuse_points, a DepthInitNet or a comparison with
+    database_depth_maps take."""
+    maps = _geo.database_depth_maps(database, ids)
+    n, h, w = maps['depth'].shape
+    out = volume.raycast(maps['poses'], maps['Ks'], h, w, min_weight, step)
+    out = {k: _geo._host(v) for k, v in out.items()}
+    return {'depth': np.ascontiguousarray(out['depth'][:, None], np.float32), 'imgs': np.ascontiguousarray(out['colors'], np.float32),
+            'poses': maps['poses'], 'Ks': maps['Ks'], 'normal': np.ascontiguousarray(out['normal'], np.float32), 'status': out['status']}
 
 
 def depth_bounds(depth, poses, Ks):
