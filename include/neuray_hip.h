@@ -585,6 +585,10 @@ int neuray_group_sum_selftest(const float* x_dev, float* y_dev, void* stream);
  * above, obtained by summing the four registers together (lane group j receives total j) and gathering the totals back into every lane;
  * y[4], y[5]: the two-value form on x[0], x[1]; y[6][l]: the lane-group sum of x[l / 16] (the scattered register itself). */
 int neuray_group_scatter_selftest(const float* x_dev, float* y_dev, void* stream);
+/* ---- self test of the point kernel's pair sites (bilinear blends, the scaled ELU, a vector row) in their packed (v_pk_mul_f32 /
+ * v_pk_fma_f32) and scalar forms on the same inputs (added within ABI 11): x [67][64] -> y [2][17][64] for the 64 lanes of one wave, form 0 =
+ * packed, form 1 = scalar; value order in csrc/nr_kernels.h (pair_forms_selftest_kernel).  The two forms agree bit for bit. */
+int neuray_pair_forms_selftest(const float* x_dev, float* y_dev, void* stream);
 
 /* ---- hardware self test of NEURAY_ARITH_X3: D [16][16] = A [16][32] @ B [32][16] through the point kernel's operand path - both operands
  * split into three bf16 parts on the device, six v_mfma_f32_16x16x32_bf16 products, fp32 accumulation.  parts_dev (may be NULL):

@@ -16,8 +16,13 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 # -ffp-contract=off: arithmetic is exactly as written (explicit fmaf where fusion is wanted), so a ray's result does
 # not depend on which tile slot / lane it lands in (hipcc otherwise SLP-packs the unrolled tile copies and contracts
 # packed and scalar leftovers differently) - required for bitwise batching / sharding invariance.
-FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-Wno-unused-value', '-Wno-pass-failed',
-         '-Wno-comment']
+# -fno-slp-vectorize: hipcc's SLP vectoriser packs adjacent scalar fp32 multiplies / adds into v_pk_mul_f32 / v_pk_add_f32 (and re-packs
+# the pair sites that csrc/nr_platform.h NR_PK_* writes as scalars).  Beside the bf16 MFMAs of the AR_X3 point kernel a packed instruction
+# is never cheaper than the scalar pair and up to 17-25 cycles dearer (tests/hw/pk_cost_probe.hip); the packing also costs the copies
+# that line the pairs up.  Without it: point kernel (x3) -0.9 %, ray kernel -12 %, fp32 point kernel unchanged.
+# Where pairs pay (the fp32 arithmetic) they are written as such (nr_v2).  Results are bit-identical either way.
+FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-fno-slp-vectorize', '-Wno-unused-value',
+         '-Wno-pass-failed', '-Wno-comment']
 
 
 OUT_BF16 = os.path.join(HERE, 'libneuray_hip_bf16.so')      # same sources with -DNR_BF16_QUADS (bf16 MFMA operands)

@@ -1160,6 +1160,10 @@ int neuray_group_sum_selftest(const float* x, float* y, void* stream) {
     NR_LAUNCH(nr::group_sum_selftest_kernel, dim3(1), dim3(64), 0, stream, x, y);
     return check_launch("neuray_group_sum_selftest");
 }
+int neuray_pair_forms_selftest(const float* x, float* y, void* stream) {
+    NR_LAUNCH(nr::pair_forms_selftest_kernel, dim3(1), dim3(64), 0, stream, x, y);
+    return check_launch("neuray_pair_forms_selftest");
+}
 int neuray_group_scatter_selftest(const float* x, float* y, void* stream) {
     NR_LAUNCH(nr::group_scatter_selftest_kernel, dim3(1), dim3(64), 0, stream, x, y);
     return check_launch("neuray_group_scatter_selftest");

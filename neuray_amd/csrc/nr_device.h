@@ -8,6 +8,9 @@
 
 namespace nr {
 
+// packed (true) or scalar (false) form of a pair site in the kernels of arithmetic `ar` (nr_platform.h NR_PK_*)
+constexpr bool pk_form(int mask, int ar) { return ((mask >> ar) & 1) != 0; }
+
 // ---------------------------------------------------------------------------------------------
 // ordered small algebra
 // ---------------------------------------------------------------------------------------------
@@ -295,24 +298,27 @@ __device__ __forceinline__ TapW2 tap_weights2(const Taps& t, float mask) {
     TapW2 w; w.w00 = nr_v2_make(a, a); w.w10 = nr_v2_make(b, b); w.w01 = nr_v2_make(c, c); w.w11 = nr_v2_make(d, d);
     return w;
 }
-__device__ __forceinline__ nr_v2 blend4_2(nr_v2 a, nr_v2 b, nr_v2 c, nr_v2 d, const TapW2& w) {
-    return nr_v2_fma(d, w.w11, nr_v2_fma(c, w.w01, nr_v2_fma(b, w.w10, nr_v2_mul(a, w.w00))));
+template <bool PK> __device__ __forceinline__ nr_v2 blend4_2(nr_v2 a, nr_v2 b, nr_v2 c, nr_v2 d, const TapW2& w) {
+    return nr_v2_fma<PK>(d, w.w11, nr_v2_fma<PK>(c, w.w01, nr_v2_fma<PK>(b, w.w10, nr_v2_mul<PK>(a, w.w00))));
 }
+// PK: packed or scalar form (NR_PK_BLEND; the point kernel passes its arithmetic's, everything else takes the fp32 setting)
+template <bool PK = pk_form(NR_PK_BLEND, AR_F32)>
 __device__ __forceinline__ void blend8(const float4 (&q)[8], const Taps& t, float mask, float (&out)[8]) {
     const TapW2 w = tap_weights2(t, mask);
     NR_PRAGMA_UNROLL
     for (int h = 0; h < 2; ++h) {            // q[h], q[2+h], q[4+h], q[6+h]: the four taps of channels 4h .. 4h+3
-        const nr_v2 lo = blend4_2(nr_v2_make(q[h].x, q[h].y), nr_v2_make(q[2 + h].x, q[2 + h].y), nr_v2_make(q[4 + h].x, q[4 + h].y),
+        const nr_v2 lo = blend4_2<PK>(nr_v2_make(q[h].x, q[h].y), nr_v2_make(q[2 + h].x, q[2 + h].y), nr_v2_make(q[4 + h].x, q[4 + h].y),
                                   nr_v2_make(q[6 + h].x, q[6 + h].y), w);
-        const nr_v2 hi = blend4_2(nr_v2_make(q[h].z, q[h].w), nr_v2_make(q[2 + h].z, q[2 + h].w), nr_v2_make(q[4 + h].z, q[4 + h].w),
+        const nr_v2 hi = blend4_2<PK>(nr_v2_make(q[h].z, q[h].w), nr_v2_make(q[2 + h].z, q[2 + h].w), nr_v2_make(q[4 + h].z, q[4 + h].w),
                                   nr_v2_make(q[6 + h].z, q[6 + h].w), w);
         out[4 * h] = lo.x; out[4 * h + 1] = lo.y; out[4 * h + 2] = hi.x; out[4 * h + 3] = hi.y;
     }
 }
+template <bool PK = pk_form(NR_PK_BLEND, AR_F32)>
 __device__ __forceinline__ void blend_rgb(const float4 (&c)[4], const Taps& t, float mask, float (&rgb)[3]) {
     const TapW2 w = tap_weights2(t, mask);
-    const nr_v2 rg = blend4_2(nr_v2_make(c[0].x, c[0].y), nr_v2_make(c[1].x, c[1].y), nr_v2_make(c[2].x, c[2].y), nr_v2_make(c[3].x, c[3].y), w);
-    const nr_v2 bb = blend4_2(nr_v2_make(c[0].z, c[0].w), nr_v2_make(c[1].z, c[1].w), nr_v2_make(c[2].z, c[2].w), nr_v2_make(c[3].z, c[3].w), w);
+    const nr_v2 rg = blend4_2<PK>(nr_v2_make(c[0].x, c[0].y), nr_v2_make(c[1].x, c[1].y), nr_v2_make(c[2].x, c[2].y), nr_v2_make(c[3].x, c[3].y), w);
+    const nr_v2 bb = blend4_2<PK>(nr_v2_make(c[0].z, c[0].w), nr_v2_make(c[1].z, c[1].w), nr_v2_make(c[2].z, c[2].w), nr_v2_make(c[3].z, c[3].w), w);
     rgb[0] = rg.x; rgb[1] = rg.y; rgb[2] = bb.x;
 }
 
@@ -554,7 +560,7 @@ __device__ __forceinline__ void layer_prefetch(WS W, int lane, VecPre<L>& p) {
     p.b = wld4(W, (lane >> 4) * 16, vec_bias_offset(L, AR) * 4);
 }
 // a[t][j] = this lane group's part of sum_f w_j[f] x[t][f] (its 4 * tiles features); x in the D layout (4 registers per tile)
-template <int L, int NT, int KX>
+template <int L, int NT, bool PK = pk_form(NR_PK_VEC, AR_F32), int KX>
 __device__ __forceinline__ void layer_vec_partial(const VecPre<L>& p, const float (&x)[NT][KX], float (&a)[NT][kVec[L].n]) {
     constexpr int N = kVec[L].n, TI = kVec[L].tiles;
     static_assert(KX >= 4 * TI, "operand array too small");
@@ -562,23 +568,24 @@ __device__ __forceinline__ void layer_vec_partial(const VecPre<L>& p, const floa
     for (int t = 0; t < NT; ++t)
         NR_PRAGMA_UNROLL
         for (int j = 0; j < N; ++j) {
-            // two products per instruction (v_pk_mul / v_pk_fma over register pairs), the halves added at the end
-            nr_v2 a2 = nr_v2_mul(nr_v2_make(p.w[j * TI].x, p.w[j * TI].y), nr_v2_make(x[t][0], x[t][1]));
-            a2 = nr_v2_fma(nr_v2_make(p.w[j * TI].z, p.w[j * TI].w), nr_v2_make(x[t][2], x[t][3]), a2);
+            // two products per instruction (v_pk_mul / v_pk_fma over register pairs; PK = false: the same pairs as scalar operations),
+            // the halves added at the end
+            nr_v2 a2 = nr_v2_mul<PK>(nr_v2_make(p.w[j * TI].x, p.w[j * TI].y), nr_v2_make(x[t][0], x[t][1]));
+            a2 = nr_v2_fma<PK>(nr_v2_make(p.w[j * TI].z, p.w[j * TI].w), nr_v2_make(x[t][2], x[t][3]), a2);
             NR_PRAGMA_UNROLL
             for (int ti = 1; ti < TI; ++ti) {
-                a2 = nr_v2_fma(nr_v2_make(p.w[j * TI + ti].x, p.w[j * TI + ti].y), nr_v2_make(x[t][4 * ti], x[t][4 * ti + 1]), a2);
-                a2 = nr_v2_fma(nr_v2_make(p.w[j * TI + ti].z, p.w[j * TI + ti].w), nr_v2_make(x[t][4 * ti + 2], x[t][4 * ti + 3]), a2);
+                a2 = nr_v2_fma<PK>(nr_v2_make(p.w[j * TI + ti].x, p.w[j * TI + ti].y), nr_v2_make(x[t][4 * ti], x[t][4 * ti + 1]), a2);
+                a2 = nr_v2_fma<PK>(nr_v2_make(p.w[j * TI + ti].z, p.w[j * TI + ti].w), nr_v2_make(x[t][4 * ti + 2], x[t][4 * ti + 3]), a2);
             }
             a[t][j] = a2.x + a2.y;
         }
 }
 // out[t][j] = b_j + sum_f w_j[f] x[t][f], identical in the four lane groups
-template <int L, int NT, int KX>
+template <int L, int NT, bool PK = pk_form(NR_PK_VEC, AR_F32), int KX>
 __device__ __forceinline__ void layer_vec(const VecPre<L>& p, const float (&x)[NT][KX], float (&out)[NT][kVec[L].n]) {
     constexpr int N = kVec[L].n;
     float a[NT][N];
-    layer_vec_partial<L, NT>(p, x, a);
+    layer_vec_partial<L, NT, PK>(p, x, a);
     NR_PRAGMA_UNROLL
     for (int t = 0; t < NT; ++t)
         NR_PRAGMA_UNROLL
@@ -591,19 +598,19 @@ __device__ __forceinline__ void layer_vec(const VecPre<L>& p, const float (&x)[N
 // slots, each in its own lane group(s), so that the activation behind the row is evaluated once instead of once per value and lane
 // group.  Every value is the sum + bias layer_vec gives, bit for bit.
 //   two rows (L_DFIN_M, L_DFIN_V): lane group 2 j + s holds row j of slot s  (g = the lane's group)
-template <int L, int KX>
+template <int L, bool PK = pk_form(NR_PK_VEC, AR_F32), int KX>
 __device__ __forceinline__ float layer_vec_scatter_2x2(const VecPre<L>& p, const float (&x)[2][KX], int g) {
     static_assert(kVec[L].n >= 2, "two rows");
     float a[2][kVec[L].n];
-    layer_vec_partial<L, 2>(p, x, a);
+    layer_vec_partial<L, 2, PK>(p, x, a);
     return nr_group_scatter4(a[0][0], a[1][0], a[0][1], a[1][1]) + (g >= 2 ? p.b.y : p.b.x);
 }
 //   one row J: lane groups s and 2 + s hold slot s
-template <int L, int J, int KX>
+template <int L, int J, bool PK = pk_form(NR_PK_VEC, AR_F32), int KX>
 __device__ __forceinline__ float layer_vec_scatter_1x2(const VecPre<L>& p, const float (&x)[2][KX]) {
     static_assert(kVec[L].n > J, "row outside the layer");
     float a[2][kVec[L].n];
-    layer_vec_partial<L, 2>(p, x, a);
+    layer_vec_partial<L, 2, PK>(p, x, a);
     return nr_group_scatter2(a[0][J], a[1][J]) + (J == 0 ? p.b.x : (J == 1 ? p.b.y : (J == 2 ? p.b.z : p.b.w)));
 }
 template <int L, int NT, class WS, int KX>
@@ -687,11 +694,11 @@ template <int A, int L> __device__ __forceinline__ float apply_act(float x) {
 }
 
 // two activations at a time: the multiply-add around the exponentials is one packed instruction for the pair (bitwise the
-// scalar result); exp2 and med3 have no packed form
-template <int A, int L> __device__ __forceinline__ void apply_act2(float x0, float x1, float& y0, float& y1) {
+// scalar result; PK = false, NR_PK_ELU: two v_fma_f32); exp2 and med3 have no packed form
+template <int A, int L, bool PK = pk_form(NR_PK_ELU, AR_F32)> __device__ __forceinline__ void apply_act2(float x0, float x1, float& y0, float& y1) {
     if (A == ACT_ELU) {
         if (kOutScaled[L]) {       // L(2^x - 1)
-            const nr_v2 f = nr_v2_fma(nr_v2_make(nr_fast_exp2(x0), nr_fast_exp2(x1)), nr_v2_make((float)kLog2e, (float)kLog2e),
+            const nr_v2 f = nr_v2_fma<PK>(nr_v2_make(nr_fast_exp2(x0), nr_fast_exp2(x1)), nr_v2_make((float)kLog2e, (float)kLog2e),
                                       nr_v2_make(-(float)kLog2e, -(float)kLog2e));
             y0 = nr_med3(x0, f.x, 0.0f); y1 = nr_med3(x1, f.y, 0.0f);
             return;
@@ -720,7 +727,7 @@ __device__ __forceinline__ void layer_fwd(WS W, int lane, const LayerPre<L>& pre
         for (int mo = 0; mo < MT; ++mo)
             NR_PRAGMA_UNROLL
             for (int r = 0; r < 4; r += 2) {
-                apply_act2<A, L>(acc[t][mo][r], acc[t][mo][r + 1], y[t][4 * mo + r], y[t][4 * mo + r + 1]);
+                apply_act2<A, L, pk_form(NR_PK_ELU, ws_ar<WS>::value)>(acc[t][mo][r], acc[t][mo][r + 1], y[t][4 * mo + r], y[t][4 * mo + r + 1]);
             }
 }
 
@@ -897,7 +904,7 @@ __device__ __forceinline__ void layer_fwd(WS W, int lane, const LayerPre3<L>& pr
         for (int mo = 0; mo < MT; ++mo)
             NR_PRAGMA_UNROLL
             for (int r = 0; r < 4; r += 2) {
-                apply_act2<A, L>(acc[t][mo][r], acc[t][mo][r + 1], y[t][4 * mo + r], y[t][4 * mo + r + 1]);
+                apply_act2<A, L, pk_form(NR_PK_ELU, AR_X3)>(acc[t][mo][r], acc[t][mo][r + 1], y[t][4 * mo + r], y[t][4 * mo + r + 1]);
             }
 }
 // y = act(scale_t * (W x) + b): a layer whose input is the operand times one scalar per (point, view) column - W (s x) = s (W x) - so that
@@ -924,7 +931,7 @@ __device__ __forceinline__ void layer_fwd_scaled(WS W, int lane, const LayerPre3
             const float b[4] = {pre.b[mo].x, pre.b[mo].y, pre.b[mo].z, pre.b[mo].w};
             NR_PRAGMA_UNROLL
             for (int r = 0; r < 4; r += 2)
-                apply_act2<A, L>(fmaf(acc[t][mo][r], scale[t], b[r]), fmaf(acc[t][mo][r + 1], scale[t], b[r + 1]), y[t][4 * mo + r], y[t][4 * mo + r + 1]);
+                apply_act2<A, L, pk_form(NR_PK_ELU, AR_X3)>(fmaf(acc[t][mo][r], scale[t], b[r]), fmaf(acc[t][mo][r + 1], scale[t], b[r + 1]), y[t][4 * mo + r], y[t][4 * mo + r + 1]);
         }
 }
 

@@ -243,6 +243,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
     constexpr int RMAX = point_rmax<NT>();
     constexpr int NS = VPW;
     constexpr bool SKIP = (NR_POINT_SKIP != 0) && !SAVE && !DBG && VPW == 2;
+    constexpr bool PKB = pk_form(NR_PK_BLEND, AR), PKV = pk_form(NR_PK_VEC, AR);      // packed or scalar pair sites (nr_platform.h; the ELU's follows the weight source)
     const int lane = threadIdx.x & 63;
     const int wave = NR_UNIFORM((int)(threadIdx.x >> 6));
     const int nw = (p.rfn + VPW - 1) / VPW;          // waves per workgroup
@@ -428,9 +429,9 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     issue8(if_map, goff, soff_f[s], tfs[s], qi);
                     issue_rgb(rgb_map, soff_c[s], tcs[s], qc4);
                     NR_PIN();
-                    blend8(qf, tfs[s], mask[s], fray[s]);
-                    blend8(qi, tfs[s], mask[s], fimg[s]);
-                    blend_rgb(qc4, tcs[s], mask[s], rgb[s]);
+                    blend8<PKB>(qf, tfs[s], mask[s], fray[s]);
+                    blend8<PKB>(qi, tfs[s], mask[s], fimg[s]);
+                    blend_rgb<PKB>(qc4, tcs[s], mask[s], rgb[s]);
                     // the blends happen HERE: left alone the img / rgb blends are sunk to their first use (ray_dir_fc, two phases
                     // later) and the 48 raw tap registers of the slot are carried - spilled - through the whole dist decoder
                     NR_PRAGMA_UNROLL
@@ -445,9 +446,9 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         issue8(rf_map, goff, soff_f[s] + 8192, tfs[s], q2);
                         issue8(rf_map, goff, soff_f[s] + 12288, tfs[s], q3);
                         NR_PIN();
-                        blend8(q1, tfs[s], mask[s], fm1[s]);
-                        blend8(q2, tfs[s], mask[s], fv1[s]);
-                        blend8(q3, tfs[s], mask[s], fa1[s]);
+                        blend8<PKB>(q1, tfs[s], mask[s], fm1[s]);
+                        blend8<PKB>(q2, tfs[s], mask[s], fv1[s]);
+                        blend8<PKB>(q3, tfs[s], mask[s], fa1[s]);
                         NR_PRAGMA_UNROLL
                         for (int k = 0; k < 8; ++k) { NR_KEEP(fm1[s][k]); NR_KEEP(fv1[s][k]); NR_KEEP(fa1[s][k]); }
                         NR_PIN();
@@ -486,8 +487,8 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
 #endif
                     layer_fwd<L_DM2, NA, ACT_ELU>(W1, lane, p_dm2, operand<AR>(h1), none, h2, p_fm);
                     layer_prefetch<L_DV1>(W1, lane, p_dv1);
-                    if constexpr (SC) mu_g = softplus(layer_vec_scatter_2x2<L_DFIN_M>(p_fm, h2, gg));
-                    else layer_vec<L_DFIN_M, NA>(p_fm, h2, fm);
+                    if constexpr (SC) mu_g = softplus(layer_vec_scatter_2x2<L_DFIN_M, PKV>(p_fm, h2, gg));
+                    else layer_vec<L_DFIN_M, NA, PKV>(p_fm, h2, fm);
 #ifdef NR_PROBE_PRE
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s)
@@ -503,9 +504,9 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     layer_prefetch<L_DV2>(W2, lane, p_dv2);
                     layer_fwd<L_DV2, NA, ACT_ELU>(W2, lane, p_dv2, operand<AR>(h1), none, h2, p_fv);
                     layer_prefetch<L_DA1>(W2, lane, p_da1);
-                    if constexpr (SC) sd_g = softplus(layer_vec_scatter_2x2<L_DFIN_V>(p_fv, h2, gg)) + pt->var_bias;
+                    if constexpr (SC) sd_g = softplus(layer_vec_scatter_2x2<L_DFIN_V, PKV>(p_fv, h2, gg)) + pt->var_bias;
                     else {
-                        layer_vec<L_DFIN_V, NA>(p_fv, h2, fv);
+                        layer_vec<L_DFIN_V, NA, PKV>(p_fv, h2, fv);
                         NR_PRAGMA_UNROLL
                         for (int s = 0; s < NA; ++s) {
                             mu0[s] = softplus(fm[s][0]); mu1[s] = softplus(fm[s][1]);
@@ -522,8 +523,8 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     layer_fwd<L_DA1, NA, ACT_ELU>(W2, lane, p_da1, o_fray, none, h1, p_da2);
 #endif
                     layer_fwd<L_DA2, NA, ACT_ELU>(W2, lane, p_da2, operand<AR>(h1), none, h2, p_fa);
-                    if constexpr (SC) aw_g = sigmoidf(layer_vec_scatter_1x2<L_DFIN_A, 0>(p_fa, h2));
-                    else layer_vec<L_DFIN_A, NA>(p_fa, h2, fa);
+                    if constexpr (SC) aw_g = sigmoidf(layer_vec_scatter_1x2<L_DFIN_A, 0, PKV>(p_fa, h2));
+                    else layer_vec<L_DFIN_A, NA, PKV>(p_fa, h2, fa);
                 }
                 if constexpr (HAS_VIS) {
                     const auto W2s = phase_enter<PH_DIST_S, HAS_VIS>(wl, W, seq0, true, wave_t, nw, lane);
@@ -533,9 +534,9 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         layer_prefetch<L_DS1>(W2s, lane, p_ds1);
                         layer_fwd<L_DS1, NA, ACT_ELU>(W2s, lane, p_ds1, o_fray, none, h1, p_ds2);
                         layer_fwd<L_DS2, NA, ACT_ELU>(W2s, lane, p_ds2, operand<AR>(h1), none, h2, p_fs);
-                        if constexpr (SC) nu_g = sigmoidf(layer_vec_scatter_1x2<L_DFIN_S, 0>(p_fs, h2));
+                        if constexpr (SC) nu_g = sigmoidf(layer_vec_scatter_1x2<L_DFIN_S, 0, PKV>(p_fs, h2));
                         else {
-                            layer_vec<L_DFIN_S, NA>(p_fs, h2, fs);
+                            layer_vec<L_DFIN_S, NA, PKV>(p_fs, h2, fs);
                             NR_PRAGMA_UNROLL
                             for (int s = 0; s < NA; ++s) { aw[s] = sigmoidf(fa[s][0]); nu[s] = sigmoidf(fs[s][0]); }
                         }
@@ -624,13 +625,13 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     layer_fwd<L_RD2, NA, ACT_ELU>(W3, lane, p_rd2, operand<AR>(h), none, df, last);
                     if constexpr (SC) {                           // the three rgb rows of ray_dir_fc.2: rows 0, 1 of both slots, then row 2
                         float a[2][3];
-                        layer_vec_partial<L_RD2, 2>(p_rd2v, h, a);
+                        layer_vec_partial<L_RD2, 2, PKV>(p_rd2v, h, a);
                         const float e01 = elu(nr_group_scatter4(a[0][0], a[1][0], a[0][1], a[1][1]) + (gg >= 2 ? p_rd2v.b.y : p_rd2v.b.x));
                         const float e2 = elu(nr_group_scatter2(a[0][2], a[1][2]) + p_rd2v.b.z);
                         nr_group_gather4(e01, dc[0][0], dc[1][0], dc[0][1], dc[1][1]);
                         nr_group_gather2(e2, dc[0][2], dc[1][2]);
                     } else {
-                        layer_vec<L_RD2, NA>(p_rd2v, h, dc);
+                        layer_vec<L_RD2, NA, PKV>(p_rd2v, h, dc);
                         NR_PRAGMA_UNROLL
                         for (int s = 0; s < NA; ++s)
                             NR_PRAGMA_UNROLL
@@ -653,9 +654,9 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                 layer_prefetch<L_NF1>(W4, lane, p_nf1);
                 if constexpr (AR == AR_X3) { e3 = split_operand(e); layer_fwd<L_NF1, NA, ACT_ELU>(W4, lane, p_nf1, e3, none, h, p_nf2); }
                 else layer_fwd<L_NF1, NA, ACT_ELU>(W4, lane, p_nf1, e, none, h, p_nf2);
-                if constexpr (SC) nr_group_gather2(sigmoidf(layer_vec_scatter_1x2<L_NF2, 0>(p_nf2, h)), sn[0], sn[1]);
+                if constexpr (SC) nr_group_gather2(sigmoidf(layer_vec_scatter_1x2<L_NF2, 0, PKV>(p_nf2, h)), sn[0], sn[1]);
                 else {
-                    layer_vec<L_NF2, NA>(p_nf2, h, o);
+                    layer_vec<L_NF2, NA, PKV>(p_nf2, h, o);
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s) sn[s] = sigmoidf(o[s][0]);
                 }
@@ -861,9 +862,9 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     layer_prefetch<L_VF2>(W5, lane, p_vf2v);
                     layer_fwd<L_VF2, NA, ACT_ELU>(W5, lane, p_vf2, operand<AR>(h), none, y, p_v21);
                     // row 32: the visibility logit; sigmoid on an ELU output: quirk A.9.4
-                    if constexpr (SC) nr_group_gather2(sigmoidf(elu(layer_vec_scatter_1x2<L_VF2, 0>(p_vf2v, h))), yv[0][0], yv[1][0]);
+                    if constexpr (SC) nr_group_gather2(sigmoidf(elu(layer_vec_scatter_1x2<L_VF2, 0, PKV>(p_vf2v, h))), yv[0][0], yv[1][0]);
                     else {
-                        layer_vec<L_VF2, NA>(p_vf2v, h, yv);
+                        layer_vec<L_VF2, NA, PKV>(p_vf2v, h, yv);
                         NR_PRAGMA_UNROLL
                         for (int s = 0; s < NA; ++s) yv[s][0] = sigmoidf(elu(yv[s][0]));
                     }
@@ -880,9 +881,9 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         layer_fwd_scaled<L_V21, NA, ACT_ELU>(W5, lane, p_v21, x3, visp, h, p_v22);       // W (x vis') = vis' (W x)
                     } else layer_fwd<L_V21, NA, ACT_ELU>(W5, lane, p_v21, xin, none, h, p_v22);
                     layer_prefetch<L_RF1>(W5, lane, p_rf1);
-                    if constexpr (SC) nr_group_gather2(sigmoidf(layer_vec_scatter_1x2<L_V22, 0>(p_v22, h)), o[0][0], o[1][0]);
+                    if constexpr (SC) nr_group_gather2(sigmoidf(layer_vec_scatter_1x2<L_V22, 0, PKV>(p_v22, h)), o[0][0], o[1][0]);
                     else {
-                        layer_vec<L_V22, NA>(p_v22, h, o);
+                        layer_vec<L_V22, NA, PKV>(p_v22, h, o);
                         NR_PRAGMA_UNROLL
                         for (int s = 0; s < NA; ++s) o[s][0] = sigmoidf(o[s][0]);
                     }
@@ -897,8 +898,8 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     if constexpr (AR == AR_X3) layer_fwd<L_RF1, NA, ACT_ELU>(W5, lane, p_rf1, x3, x1, h16, p_rf2);
                     else layer_fwd<L_RF1, NA, ACT_ELU>(W5, lane, p_rf1, x, x1, h16, p_rf2);
                     layer_fwd<L_RF2, NA, ACT_ELU>(W5, lane, p_rf2, operand<AR>(h16), none, h8, p_rf3);
-                    if constexpr (SC) nr_group_gather2(layer_vec_scatter_1x2<L_RF3, 0>(p_rf3, h8), o[0][0], o[1][0]);
-                    else layer_vec<L_RF3, NA>(p_rf3, h8, o);
+                    if constexpr (SC) nr_group_gather2(layer_vec_scatter_1x2<L_RF3, 0, PKV>(p_rf3, h8), o[0][0], o[1][0]);
+                    else layer_vec<L_RF3, NA, PKV>(p_rf3, h8, o);
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s) {
                         z[s] = mask[s] > 0.0f ? o[s][0] : -1e9f;
@@ -1888,6 +1889,46 @@ __global__ void x3_selftest_kernel(const float* __restrict__ A /*16x32*/, const 
 
 __global__ void group_sum_selftest_kernel(const float* __restrict__ x, float* __restrict__ y) {
     y[threadIdx.x & 63] = nr_group_sum(x[threadIdx.x & 63]);
+}
+
+// The pair sites of the point kernel (nr_platform.h NR_PK_BLEND / NR_PK_ELU / NR_PK_VEC) in BOTH forms on the same inputs: x [67][64] ->
+// y [2][17][64], form 0 = packed (v_pk_mul_f32 / v_pk_fma_f32), form 1 = the scalar pairs; the two have to agree bit for bit.  Per lane l,
+// x[i][l]: i = 0..31 the eight float4 taps of blend8 (the first four are blend_rgb's), 32..35 the tap weights, 36 the validity mask, 37, 38
+// the scaled-ELU pair, 39..54 the four float4 weights of L_DFIN_M's two rows, 55..62 their operand, 63..66 the bias.  y[f][i][l]: i = 0..7
+// blend8, 8..10 blend_rgb, 11, 12 apply_act2, 13, 14 layer_vec_partial, 15, 16 layer_vec.
+template <bool PK> __device__ __forceinline__ void pair_forms_eval(const float* __restrict__ x, int l, float (&o)[17]) {
+    auto in = [&](int i) { return x[i * 64 + l]; };
+    float4 q[8], c4[4];
+    for (int i = 0; i < 8; ++i) q[i] = make_float4(in(4 * i), in(4 * i + 1), in(4 * i + 2), in(4 * i + 3));
+    for (int i = 0; i < 4; ++i) c4[i] = q[i];
+    Taps t;
+    t.o00 = t.o10 = t.o01 = t.o11 = 0;
+    t.w00 = in(32); t.w10 = in(33); t.w01 = in(34); t.w11 = in(35);
+    const float mask = in(36);
+    float b8[8], rgb[3];
+    blend8<PK>(q, t, mask, b8);
+    blend_rgb<PK>(c4, t, mask, rgb);
+    for (int i = 0; i < 8; ++i) o[i] = b8[i];
+    for (int i = 0; i < 3; ++i) o[8 + i] = rgb[i];
+    static_assert(kOutScaled[L_DM1], "the scaled ELU is the pair site");
+    apply_act2<ACT_ELU, L_DM1, PK>(in(37), in(38), o[11], o[12]);
+    static_assert(kVec[L_DFIN_M].n == 2 && kVec[L_DFIN_M].tiles == 2, "two rows over two tiles");
+    VecPre<L_DFIN_M> p;
+    for (int i = 0; i < 4; ++i) p.w[i] = make_float4(in(39 + 4 * i), in(40 + 4 * i), in(41 + 4 * i), in(42 + 4 * i));
+    p.b = make_float4(in(63), in(64), in(65), in(66));
+    float xv[1][8], a[1][2], out[1][2];
+    for (int i = 0; i < 8; ++i) xv[0][i] = in(55 + i);
+    layer_vec_partial<L_DFIN_M, 1, PK>(p, xv, a);
+    layer_vec<L_DFIN_M, 1, PK>(p, xv, out);
+    o[13] = a[0][0]; o[14] = a[0][1]; o[15] = out[0][0]; o[16] = out[0][1];
+}
+__global__ void pair_forms_selftest_kernel(const float* __restrict__ x, float* __restrict__ y) {
+    const int l = threadIdx.x & 63;
+    float o[17];
+    pair_forms_eval<true>(x, l, o);
+    for (int i = 0; i < 17; ++i) y[i * 64 + l] = o[i];
+    pair_forms_eval<false>(x, l, o);
+    for (int i = 0; i < 17; ++i) y[(17 + i) * 64 + l] = o[i];
 }
 
 // the batched forms (nr_platform.h): x [4][64] -> y [7][64].  Rows 0..3: the four-value reduce-scatter of x[0..3] handed back by the

@@ -150,18 +150,43 @@ __device__ __forceinline__ void nr_gst4(NR_GLOBAL_PTR(float) p, float4 v) {
 
 #define NR_WAVE 64
 
-// ---- two fp32 values per instruction (v_pk_mul_f32 / v_pk_fma_f32: full-rate on CDNA3/4, i.e. twice the scalar VALU
-// throughput).  Each half is the IEEE result of the scalar operation, so packed and scalar code are bitwise equal.
+// ---- two fp32 values per instruction (v_pk_mul_f32 / v_pk_fma_f32).  Each half is the IEEE result of the scalar operation, so packed
+// and scalar code are bitwise equal (tests/test_pair_forms.py).  What a packed instruction COSTS depends on what it is issued next to
+// (tests/hw/pk_cost_probe.hip): in a VALU-only stream it is the price of two scalar ones (the data sheet's "full
+// rate"); between fp32 16x16x4 MFMAs likewise (7.6 against 2 x 3.8 cycles); between the v_mfma_f32_16x16x32_bf16 of AR_X3 a single one
+// in an MFMA's shadow costs 17 SIMD cycles at one wave per SIMD and 25 at two, where the scalar pair costs about 1, and in a dense
+// VALU stretch still 7.6 against 6.1 (11.0 against 8.4 at two waves) - never cheaper there.  Hence the three sites that are written in
+// pairs choose their form per arithmetic: bit (1 << AR) of a switch set = packed in the kernels of that arithmetic (nr_layout.h AR_F32 =
+// 0: fp32 MFMA - training forward, one-view-per-wave kernels and everything outside the point kernel included -, AR_X3 = 1).
+//   NR_PK_BLEND  blend8 / blend_rgb (nr_device.h)      NR_PK_ELU  the scaled ELU of apply_act2      NR_PK_VEC  layer_vec rows
+// Measured in the point kernel (tools/ab_forward.py): AR_X3 - the ELU's multiply-add is faster as two
+// v_fma_f32 (-0.8 %), the blends are even and the rows slower in scalar form, so both stay packed; fp32 - every site is faster or even packed.
+#ifndef NR_PK_BLEND
+#define NR_PK_BLEND 3
+#endif
+#ifndef NR_PK_ELU
+#define NR_PK_ELU 1
+#endif
+#ifndef NR_PK_VEC
+#define NR_PK_VEC 3
+#endif
 #ifdef NEURAY_EMU
 struct nr_v2 { float x, y; };
 static inline nr_v2 nr_v2_make(float a, float b) { return nr_v2{a, b}; }
-static inline nr_v2 nr_v2_mul(nr_v2 a, nr_v2 b) { return nr_v2{__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)}; }
-static inline nr_v2 nr_v2_fma(nr_v2 a, nr_v2 b, nr_v2 c) { return nr_v2{fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y)}; }
+template <bool PK = true> static inline nr_v2 nr_v2_mul(nr_v2 a, nr_v2 b) { return nr_v2{__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)}; }
+template <bool PK = true> static inline nr_v2 nr_v2_fma(nr_v2 a, nr_v2 b, nr_v2 c) { return nr_v2{fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y)}; }
 #else
 typedef float nr_v2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ nr_v2 nr_v2_make(float a, float b) { nr_v2 v; v.x = a; v.y = b; return v; }
-__device__ __forceinline__ nr_v2 nr_v2_mul(nr_v2 a, nr_v2 b) { return a * b; }
-__device__ __forceinline__ nr_v2 nr_v2_fma(nr_v2 a, nr_v2 b, nr_v2 c) { return __builtin_elementwise_fma(a, b, c); }
+// PK = false: the two scalar operations, in the same order
+template <bool PK = true> __device__ __forceinline__ nr_v2 nr_v2_mul(nr_v2 a, nr_v2 b) {
+    if constexpr (PK) return a * b;
+    else return nr_v2_make(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y));
+}
+template <bool PK = true> __device__ __forceinline__ nr_v2 nr_v2_fma(nr_v2 a, nr_v2 b, nr_v2 c) {
+    if constexpr (PK) return __builtin_elementwise_fma(a, b, c);
+    else return nr_v2_make(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y));
+}
 #endif
 
 // ---- read-only buffers addressed as {SGPR descriptor, one per-lane byte offset VGPR, scalar byte offset} --------

@@ -1,6 +1,6 @@
 """Instruction classes of one kernel instantiation, from hipcc's gfx950 assembly.  Needs no GPU.
 
-    python tools/isa_classes.py [--kernel 'points_kernel<1,2,false,1,512,2,false,true,1>'] [-DNAME=VALUE ...]
+    python tools/isa_classes.py [--kernel 'points_kernel<1,2,false,1,512,2,false,true,1>'] [-DNAME=VALUE ...] [-fFLAG ...]
                                 [--json OUT.json] [--against PARENT.json] [--keep-asm FILE.s]
 
 Compiles a translation unit that holds nothing but the named instantiation (a kernel template of neuray_amd/csrc/nr_kernels.h in
@@ -182,7 +182,7 @@ def main():
     ap.add_argument('--against')
     ap.add_argument('--keep-asm')
     a, rest = ap.parse_known_args()
-    defines = [x for x in rest if x.startswith('-D')]
+    defines = [x for x in rest if x.startswith('-D') or x.startswith('-f') or x.startswith('-m')]   # (-f... / -m...: code-generation flags under trial)
     asm = assembly(a.kernel, defines)
     if a.keep_asm:
         open(a.keep_asm, 'w').write(asm)

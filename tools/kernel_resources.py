@@ -1,6 +1,6 @@
 """Register / spill / scratch / occupancy table of the library's kernels, from hipcc's own remarks.
 
-    python tools/kernel_resources.py [-DNAME=VALUE ...] [--filter substring]
+    python tools/kernel_resources.py [-DNAME=VALUE ...] [-fFLAG ...] [--filter substring]
 
 Compiles neuray_amd/csrc/neuray_hip.hip for gfx950 with -Rpass-analysis=kernel-resource-usage (device code only, no link) and
 prints one line per kernel: VGPRs, AGPRs, spilled VGPRs / SGPRs, scratch bytes per lane, occupancy (waves per SIMD), LDS bytes."""
@@ -33,7 +33,7 @@ def resources(extra=()):
 
 
 def main():
-    extra = [a for a in sys.argv[1:] if a.startswith('-D')]
+    extra = [a for a in sys.argv[1:] if a.startswith('-D') or a.startswith('-f')]       # (-f...: code-generation flags under trial)
     filt = sys.argv[sys.argv.index('--filter') + 1] if '--filter' in sys.argv else ''
     rows = [r for r in resources(extra) if filt.lower() in r['name'].lower()]      # (the whole signature, any case)
     print('%-100s %5s %5s %6s %6s %8s %4s %7s' % ('kernel', 'VGPR', 'AGPR', 'vspill', 'sspill', 'scratch', 'occ', 'LDS'))
