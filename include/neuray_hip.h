@@ -589,6 +589,13 @@ int neuray_group_scatter_selftest(const float* x_dev, float* y_dev, void* stream
  * v_pk_fma_f32) and scalar forms on the same inputs (added within ABI 11): x [67][64] -> y [2][17][64] for the 64 lanes of one wave, form 0 =
  * packed, form 1 = scalar; value order in csrc/nr_kernels.h (pair_forms_selftest_kernel).  The two forms agree bit for bit. */
 int neuray_pair_forms_selftest(const float* x_dev, float* y_dev, void* stream);
+/* ---- self test of the two forms of the point kernel's cross-view all-reduce (two barriers / one barrier over two LDS banks; added within
+ * ABI 11): one workgroup of nw waves (1..8) runs the kernel's sequence of a tile - 12, 11, 11, 11 rows summed, 2 rows of which row 0 takes
+ * the maximum, 12, 8 rows summed - twice, 14 calls, in both forms, its waves idling for different times between the calls.
+ * x [14][nw][12][64] (call, wave, row, lane; rows beyond a call's count are not read) -> y [2][14][nw][12][64]: what every wave and lane
+ * holds after each call, form 0 = two barriers, form 1 = one barrier (rows beyond the count are not written).  Every wave holds the
+ * combination of the nw inputs in wave order, and the two forms agree bit for bit. */
+int neuray_allreduce_selftest(const float* x_dev, float* y_dev, int nw, void* stream);
 
 /* ---- hardware self test of NEURAY_ARITH_X3: D [16][16] = A [16][32] @ B [32][16] through the point kernel's operand path - both operands
  * split into three bf16 parts on the device, six v_mfma_f32_16x16x32_bf16 products, fp32 accumulation.  parts_dev (may be NULL):

@@ -232,6 +232,7 @@ SYMBOLS = {
     'neuray_group_sum_selftest': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'neuray_group_scatter_selftest': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'neuray_pair_forms_selftest': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'neuray_allreduce_selftest': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'neuray_warp_variance': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_void_p, C.c_void_p]),
     'neuray_warp_variance_layout': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

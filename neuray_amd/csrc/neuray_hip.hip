@@ -86,11 +86,11 @@ static_assert(NEURAY_FUSE_MAX_SRC == nr::kFuseMaxSrc, "abi");
 #endif
 static_assert(NEURAY_PROC_HEADER == nr::kProcHeader && NEURAY_PROC_PRIM == nr::kProcPrim && NEURAY_PROC_MAX_PRIMS == nr::kProcMaxPrims, "abi");
 
-template <int NT, int VPW, bool HAS_VIS, int OWN, int MINW, bool SAVE = false, int AR = nr::AR_F32>
-int launch_points_own(const nr::PointParams& p, void* stream) {
+template <int NT, int VPW, bool HAS_VIS, int OWN, int MINW, bool SAVE, int AR, bool ONEB>
+int launch_points_form(const nr::PointParams& p, void* stream) {
     const int npts = p.rn * p.dn;
     const int nwaves = (p.rfn + VPW - 1) / VPW;
-    const size_t smem = nr::point_smem_bytes<NT>(nwaves, AR);
+    const size_t smem = nr::point_smem_bytes<NT>(nwaves, AR, ONEB);
     if (smem > 160 * 1024) return fail("neuray_render_points: %zu bytes of LDS needed (rfn=%d)", smem, p.rfn);
     // persistent-style grid: enough workgroups to fill the 768 resident slots (3 per CU) twenty times over, grid-stride beyond.  Measured on
     // the 800 x 800 workload (131 072 tiles per coarse launch), same box: 768 workgroups 2.30 M rays/s, 1536 2.35, 3072 / 3840 2.38,
@@ -108,14 +108,28 @@ int launch_points_own(const nr::PointParams& p, void* stream) {
     grid = (grid + 7) / 8 * 8;                         // the XCD-aware tile map needs a multiple of 8
     const int threads = 64 * nwaves;
     // __launch_bounds__(1024) caps the kernel at 128 VGPRs so that 4 waves share a SIMD (DESIGN.md "occupancy")
-    auto k = nr::points_kernel<NT, VPW, HAS_VIS, OWN, 1024 / VPW, MINW, SAVE, false, AR>;
+    auto k = nr::points_kernel<NT, VPW, HAS_VIS, OWN, 1024 / VPW, MINW, SAVE, false, AR, ONEB>;
     if constexpr (!SAVE) {
-        if (p.dbg) k = nr::points_kernel<NT, VPW, HAS_VIS, OWN, 1024 / VPW, MINW, false, true, AR>;     // the per-view record: its own instantiation
+        if (p.dbg) k = nr::points_kernel<NT, VPW, HAS_VIS, OWN, 1024 / VPW, MINW, false, true, AR, ONEB>;     // the per-view record: its own instantiation
     } else if (p.dbg) {
         return fail("neuray_render_points: dbg_dev and saved_dev together are not built (run the pass twice)");
     }
     launch_lds(k, dim3(grid), dim3(threads), smem, stream, p);
     return check_launch("neuray_render_points");
+}
+
+// The form of the cross-view all-reduces (nr_device.h): one barrier where the two banks fit (nr::point_one_barrier: the AR_X3 kernel up to
+// six waves), two barriers elsewhere.  NEURAY_POINT_ALLREDUCE=2 forces the two-barrier form from the same library (A/B hook of
+// tools/ab_forward.py and tests/test_allreduce_forms.py, read at every launch so that one process can run both); the results are
+// bit-identical.
+template <int NT, int VPW, bool HAS_VIS, int OWN, int MINW, bool SAVE = false, int AR = nr::AR_F32>
+int launch_points_own(const nr::PointParams& p, void* stream) {
+    if constexpr (AR == nr::AR_X3) {
+        const char* e = getenv("NEURAY_POINT_ALLREDUCE");
+        if (!(e && atoi(e) == 2) && nr::point_one_barrier<NT>((p.rfn + VPW - 1) / VPW, AR))
+            return launch_points_form<NT, VPW, HAS_VIS, OWN, MINW, SAVE, AR, true>(p, stream);
+    }
+    return launch_points_form<NT, VPW, HAS_VIS, OWN, MINW, SAVE, AR, false>(p, stream);
 }
 
 template <int NT, int VPW, bool HAS_VIS, int MINW, int AR = nr::AR_F32>
@@ -814,6 +828,15 @@ int neuray_x3_selftest(const float* A, const float* B, float* D, float* parts, v
     return check_launch("neuray_x3_selftest");
 }
 
+int neuray_allreduce_selftest(const float* x, float* y, int nw, void* stream) {
+    if (!x || !y) return fail("neuray_allreduce_selftest: null pointer");
+    if (nw < 1 || nw > 8) return fail("neuray_allreduce_selftest: nw=%d outside [1,8]", nw);
+    const size_t smem = nr::allreduce_selftest_smem_bytes(nw);
+    if (smem > 64 * 1024) allow_lds(nr::allreduce_selftest_kernel, smem);
+    NR_LAUNCH(nr::allreduce_selftest_kernel, dim3(1), dim3(64 * nw), smem, stream, x, y, nw);
+    return check_launch("neuray_allreduce_selftest");
+}
+
 int neuray_points_resident_workgroups(int arith, int rfn) {
 #ifdef NEURAY_EMU
     (void)arith; (void)rfn;
@@ -826,8 +849,9 @@ int neuray_points_resident_workgroups(int arith, int rfn) {
 #ifdef NR_BF16_QUADS
         return -1;
 #else
-        auto k = nr::points_kernel<1, 2, false, 1, 512, NR_POINT_MINW_X3, false, false, nr::AR_X3>;
-        const size_t smem = nr::point_smem_bytes<1>(4, nr::AR_X3);
+        if (!nr::point_one_barrier<1>(4, nr::AR_X3)) return -1;      // (the product form at four waves: launch_points_own)
+        auto k = nr::points_kernel<1, 2, false, 1, 512, NR_POINT_MINW_X3, false, false, nr::AR_X3, true>;
+        const size_t smem = nr::point_smem_bytes<1>(4, nr::AR_X3, true);
         if (smem > 64 * 1024) allow_lds(k, smem);
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 256, smem);
 #endif

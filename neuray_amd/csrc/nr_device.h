@@ -1031,4 +1031,60 @@ __device__ __forceinline__ void block_allreduce(float (&v)[R], float* red, int w
     NR_PRIO_LO();
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same all-reduce with ONE barrier: every wave writes its partial rows, one barrier, then every wave reads the nw partials
+// of every row itself and combines them in wave order 0..nw-1 - the order of the reduce-scatter loop above, so every bit is the
+// same.  Nothing is written back and there is no second barrier: the dependent LDS write -> barrier -> LDS read round trip of the
+// all-gather is gone, for nw times the reads.  Rows travel four to a float4 (quad q of wave w at [(w * RMAX / 4 + q) * 64 + lane]:
+// ds_write_b128 / ds_read_b128, conflict-free, a quarter of the instructions); the padding rows of the last quad are zeros
+// nobody uses.
+//   banks: TWO banks of nw * RMAX * 64 floats; `bank` is the running parity of the calls, the same in every wave (every wave
+//   makes the same calls), toggled here.
+// Why two banks are enough.  Call i uses bank i & 1.  A wave writes its rows of call i + 2 - the same bank as call i - only after
+// it has passed the barrier of call i + 1.  Every sibling arrived at that barrier after its reads of call i had LANDED:
+// NR_LDS_LANDED below waits on the LDS counter (and pins the reads above it) before the wave goes on to anything, its next
+// barrier arrival included.  So no read of call i can still be on its way when a row of call i + 2 overwrites what it reads;
+// and the rows of call i + 1 are in the other bank.  Barriers of other kinds between two calls only add to that.  With one bank
+// a fast wave would pass the barrier of call i, read, and write its rows of call i + 1 while a slow sibling still reads call i.
+// ---------------------------------------------------------------------------------------------
+template <int R, int RMAX, int OP, int MAXSTRIDE = 1>
+__device__ __forceinline__ void block_allreduce_1b(float (&v)[R], float* banks, int& bank, int wave, int nw, int lane) {
+    static_assert(R <= RMAX && RMAX % 4 == 0, "allreduce banks too small");
+    constexpr int Q = (R + 3) / 4, QMAX = RMAX / 4;
+    float4* b4 = reinterpret_cast<float4*>(banks + (size_t)bank * nw * (RMAX * 64)) + lane;
+    bank ^= 1;
+    NR_PRIO_HI();
+    NR_PRAGMA_UNROLL
+    for (int q = 0; q < Q; ++q)
+        b4[(wave * QMAX + q) * 64] = make_float4(v[4 * q], 4 * q + 1 < R ? v[4 * q + 1] : 0.0f, 4 * q + 2 < R ? v[4 * q + 2] : 0.0f,
+                                                 4 * q + 3 < R ? v[4 * q + 3] : 0.0f);
+    NR_BLOCK_SYNC();
+    float4 s[Q];
+    NR_PRAGMA_UNROLL
+    for (int q = 0; q < Q; ++q) s[q] = b4[q * 64];
+    auto add_wave = [&](int w) {
+        NR_PRAGMA_UNROLL
+        for (int q = 0; q < Q; ++q) {
+            const float4 t = b4[(w * QMAX + q) * 64];
+            s[q].x = red_combine<OP, MAXSTRIDE>(s[q].x, t.x, 4 * q);
+            s[q].y = red_combine<OP, MAXSTRIDE>(s[q].y, t.y, 4 * q + 1);
+            s[q].z = red_combine<OP, MAXSTRIDE>(s[q].z, t.z, 4 * q + 2);
+            s[q].w = red_combine<OP, MAXSTRIDE>(s[q].w, t.w, 4 * q + 3);
+        }
+    };
+    if (nw == 4) {          // (the headline shape, 7 or 8 views: a constant trip count, so all its reads are in flight together)
+        NR_PRAGMA_UNROLL
+        for (int w = 1; w < 4; ++w) add_wave(w);
+    } else {
+        for (int w = 1; w < nw; ++w) add_wave(w);
+    }
+    NR_LDS_LANDED();
+    NR_PRAGMA_UNROLL
+    for (int r = 0; r < R; ++r) {
+        const float4 t = s[r >> 2];
+        v[r] = (r & 3) == 0 ? t.x : ((r & 3) == 1 ? t.y : ((r & 3) == 2 ? t.z : t.w));
+    }
+    NR_PRIO_LO();
+}
+
 }  // namespace nr

@@ -121,11 +121,20 @@ __device__ __forceinline__ float sel4(int g, float a, float b, float c, float d)
 template <int NT>
 constexpr int point_rmax() { return 12 * NT; }
 
-// AR_X3: the 16-row exchange buffer lives inside the all-reduce scratch (points_kernel xrow), which makes room for the larger weight stage
+// LDS of a point-kernel workgroup: all-reduce rows | 16-row exchange buffer | the two weight-stage regions.
+//   two-barrier all-reduces (block_allreduce): nwaves + 1 regions of RMAX rows.  AR_X3: the exchange buffer lives inside them
+//   (points_kernel xrow), which makes room for the larger weight stage.
+//   one-barrier all-reduces (block_allreduce_1b; oneb): two banks of nwaves regions, and the exchange buffer has rows of its own.
 template <int NT>
-inline size_t point_smem_bytes(int nwaves, int ar = AR_F32) {
-    return sizeof(float) * (64 * ((size_t)(nwaves + 1) * point_rmax<NT>() + (ar == AR_X3 ? 0 : 16 * NT)) + weight_lds_floats(ar));
+inline size_t point_smem_bytes(int nwaves, int ar = AR_F32, bool oneb = false) {
+    const size_t red_rows = oneb ? 2 * (size_t)nwaves * point_rmax<NT>() : (size_t)(nwaves + 1) * point_rmax<NT>();
+    return sizeof(float) * (64 * (red_rows + (ar == AR_X3 && !oneb ? 0 : 16 * NT)) + weight_lds_floats(ar));
 }
+// The one-barrier form is taken where its two banks still leave the AR_X3 kernel its two workgroups per CU (80 of the 160 KiB each): up
+// to six waves; 13 to 16 views keep the two-barrier form and their second workgroup.  The fp32 instantiations (training forward, record
+// kernels, three workgroups per CU) keep the two-barrier form, its layout and its byte count.
+template <int NT>
+inline bool point_one_barrier(int nwaves, int ar) { return ar == AR_X3 && 2 * point_smem_bytes<NT>(nwaves, ar, true) <= 160 * 1024; }
 
 // owner waves accumulate one cross-view statistic (8 image channels in gathered order + 3 rgb channels per tile)
 // into their tile(s) of base_fc.0's per-point part: statistic STAT uses quads [2*STAT, 2*STAT+2) and single STAT
@@ -189,8 +198,9 @@ __device__ __forceinline__ void bg_accumulate(const BgResident<OWN>& r, int g, i
 // sum (or max; RED_MAX0: row 0 max, the other rows sum) over the NA ACTIVE view slots of the wave, then over the waves of the
 // workgroup.  The IDLE = slots - NA skipped slots of a wave (points_kernel "slot skipping") contribute what a fully masked view
 // contributes in the reference: exact zeros to every sum and the masked_fill value -1e9 (ibrnet.py:365) to the maximum row.
-template <int NA, int IDLE, int R, int RMAX, int OP>
-__device__ __forceinline__ void view_allreduce(const float (&v)[NA > 0 ? NA : 1][R], float (&out)[R], float* red, int wave,
+// ONEB: the one-barrier form (block_allreduce_1b: red = its two banks, bank = the running parity of the kernel's calls)
+template <bool ONEB, int NA, int IDLE, int R, int RMAX, int OP>
+__device__ __forceinline__ void view_allreduce(const float (&v)[NA > 0 ? NA : 1][R], float (&out)[R], float* red, int& bank, int wave,
                                                int nw, int lane) {
     NR_PRAGMA_UNROLL
     for (int r = 0; r < R; ++r) {
@@ -201,7 +211,8 @@ __device__ __forceinline__ void view_allreduce(const float (&v)[NA > 0 ? NA : 1]
         if (IDLE > 0 && NA > 0 && is_max) a = fmaxf(a, -1e9f);
         out[r] = a;
     }
-    block_allreduce<R, RMAX, OP, R>(out, red, wave, nw, lane);
+    if constexpr (ONEB) block_allreduce_1b<R, RMAX, OP, R>(out, red, bank, wave, nw, lane);
+    else block_allreduce<R, RMAX, OP, R>(out, red, wave, nw, lane);
 }
 
 template <int N> struct SlotCount { static constexpr int value = N; };
@@ -235,10 +246,13 @@ template <int N> struct SlotCount { static constexpr int value = N; };
 //   the layer is skipped and prob_embed.0's ReLU output takes its place.
 //   AR = arithmetic of the MFMA layers (nr_layout.h): AR_F32, or AR_X3 = three-way split bf16 operands on v_mfma_f32_16x16x32_bf16
 //   (p.weights is then the split pack of neuray_pack_pass_weights_x3: inference, always folded).
-template <int NT, int VPW, bool HAS_VIS, int OWN, int MAXT, int MINW, bool SAVE = false, bool DBG = false, int AR = AR_F32>
+//   ONEB = the seven cross-view all-reduces of a tile take the one-barrier form (nr_device.h block_allreduce_1b; LDS layout:
+//   point_smem_bytes), chosen by the launcher where the two banks fit (point_one_barrier).  Results are bit-identical to the two-barrier form.
+template <int NT, int VPW, bool HAS_VIS, int OWN, int MAXT, int MINW, bool SAVE = false, bool DBG = false, int AR = AR_F32, bool ONEB = false>
 __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
     static_assert(NT == 1, "one 16-point tile per wave iteration");
     static_assert(AR == AR_F32 || !SAVE, "the training forward runs on the fp32 MFMA");
+    static_assert(AR == AR_X3 || !ONEB, "the fp32 instantiations keep the two-barrier all-reduce and its LDS layout");
     NR_DYNAMIC_SMEM(float, smem);
     constexpr int RMAX = point_rmax<NT>();
     constexpr int NS = VPW;
@@ -248,19 +262,25 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
     const int wave = NR_UNIFORM((int)(threadIdx.x >> 6));
     const int nw = (p.rfn + VPW - 1) / VPW;          // waves per workgroup
     const int g = lane >> 4, c = lane & 15;
-    float* red = smem;
-    float* xch = smem + (size_t)(nw + 1) * RMAX * 64;
-    float* wl = xch + (AR == AR_X3 ? 0 : 16 * NT * 64);      // staged weights of the current phase
+    constexpr bool XCH_IN_RED = AR == AR_X3 && !ONEB;       // the exchange rows live inside the all-reduce scratch
+    float* red = smem;                                      // ONEB: the two banks of block_allreduce_1b
+    int ar_bank = 0;                                        // ... and the parity of the all-reduces made so far: seven per tile, an odd count, so it runs on across tiles
+    float* xch = smem + (size_t)(ONEB ? 2 * nw : nw + 1) * RMAX * 64;
+    float* wl = xch + (XCH_IN_RED ? 0 : 16 * NT * 64);       // staged weights of the current phase
     // the 16 rows through which the owner waves hand base_fc.0's per-point part / geometry_fc.0's hidden layer to the others: row
-    // 4 mo + r of tile mo.  AR_X3: inside the all-reduce scratch, in the region of the wave that owns the tile (mo = wave + j nw -> its
+    // 4 mo + r of tile mo.  Rows of their own (fp32, and AR_X3 with one-barrier all-reduces): the owners write them, then comes a barrier, then
+    // the others read them (tiles 2, 3 of base_fc.0 a phase barrier later still); the next writes - the other use of the rows, or the next tile's
+    // - come at least one further workgroup barrier later, at which every reader arrives with its reads landed (the barrier's fence waits for the
+    // wave's LDS reads), so no row is overwritten under a reader.  Nothing here depends on the form of the all-reduces.
+    // AR_X3 with two-barrier all-reduces: inside the all-reduce scratch, in the region of the wave that owns the tile (mo = wave + j nw -> its
     // rows 4 j + r; with one wave the 16 rows run on into the result region).  A wave's region is read by others only between the two
     // barriers of an all-reduce, the rows are written after one and consumed before the next phase barrier: no extra synchronisation.
     auto xrow = [&](int mo, int r) -> float* {
         // (OWN == 1: four or more waves, tile mo belongs to wave mo - the row is a compile-time constant for the callers' constant mo, r.
         // Left to the general form, hipcc evaluates the twelve quotient / remainder offsets of mo = 1..3 in the prologue and parks them
         // in VGPR lanes for the whole tile loop: a v_readlane per use)
-        if constexpr (AR == AR_X3 && OWN == 1) return red + ((size_t)mo * RMAX + r) * 64;
-        else if constexpr (AR == AR_X3) return red + ((size_t)(mo % nw) * RMAX + (mo / nw) * 4 + r) * 64;
+        if constexpr (XCH_IN_RED && OWN == 1) return red + ((size_t)mo * RMAX + r) * 64;
+        else if constexpr (XCH_IN_RED) return red + ((size_t)(mo % nw) * RMAX + (mo / nw) * 4 + r) * 64;
         else return xch + (mo * 4 + r) * 64;
     };
     auto make_w = [&]() {
@@ -690,7 +710,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         for (int j = 0; j < 3; ++j) p12[s][8 + j] = gr[s][j] * w_;
                         p12[s][11] = mask[s];
                     }
-                    view_allreduce<NA, IDLE, 12, RMAX, RED_SUM>(p12, o12, red, wave_t, nw, lane);
+                    view_allreduce<ONEB, NA, IDLE, 12, RMAX, RED_SUM>(p12, o12, red, ar_bank, wave_t, nw, lane);
                     msum = o12[11];
                     const float inv = nr_fast_rcp(msum + 1e-8f);
                     NR_PRAGMA_UNROLL
@@ -714,7 +734,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                             NR_PRAGMA_UNROLL
                             for (int j = 0; j < 3; ++j) part[s][8 + j] = gr[s][j] * wk[s];
                         }
-                        view_allreduce<NA, IDLE, 11, RMAX, RED_SUM>(part, st, red, wave_t, nw, lane);
+                        view_allreduce<ONEB, NA, IDLE, 11, RMAX, RED_SUM>(part, st, red, ar_bank, wave_t, nw, lane);
                     }
                     NR_PRAGMA_UNROLL
                     for (int s = 0; s < NA; ++s) {
@@ -730,7 +750,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         if (k == 0) bg_accumulate<NT, OWN, 0>(W, glane, gg, wave_t, nw, st, accg);
                         else bg_accumulate<NT, OWN, 2>(W, glane, gg, wave_t, nw, st, accg);
                     }
-                    view_allreduce<NA, IDLE, 11, RMAX, RED_SUM>(part, sv, red, wave_t, nw, lane);
+                    view_allreduce<ONEB, NA, IDLE, 11, RMAX, RED_SUM>(part, sv, red, ar_bank, wave_t, nw, lane);
                     if constexpr (BG_RES) {
                         if (k == 0) bg_accumulate<NT, OWN, 1>(bgres, gg, wave_t, nw, sv, accg);
                         else bg_accumulate<NT, OWN, 3>(bgres, gg, wave_t, nw, sv, accg);
@@ -924,7 +944,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     z2[s][0] = z[s]; z2[s][1] = vis2[s];
                     if constexpr (SAVE) z2[s][2] = sn[s] * wv[s];
                 }
-                view_allreduce<NA, IDLE, ZR, RMAX, RED_MAX0>(z2, zv, red, wave_t, nw, lane);
+                view_allreduce<ONEB, NA, IDLE, ZR, RMAX, RED_MAX0>(z2, zv, red, ar_bank, wave_t, nw, lane);
                 float b12[NA1][12];
                 NR_PRAGMA_UNROLL
                 for (int s = 0; s < NA; ++s) {
@@ -947,14 +967,14 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         NR_PRAGMA_UNROLL
                         for (int i = 1; i < IDLE; ++i) acc_ += ev_idle;
                         b12[0][8] = acc_;
-                        view_allreduce<1, 0, 12, RMAX, RED_SUM>(b12, big, red, wave_t, nw, lane);
+                        view_allreduce<ONEB, 1, 0, 12, RMAX, RED_SUM>(b12, big, red, ar_bank, wave_t, nw, lane);
                     } else {
                         NR_PRAGMA_UNROLL
                         for (int i = 0; i < IDLE; ++i) b12[NA - 1][8] += ev_idle;
-                        view_allreduce<NA, 0, 12, RMAX, RED_SUM>(b12, big, red, wave_t, nw, lane);
+                        view_allreduce<ONEB, NA, 0, 12, RMAX, RED_SUM>(b12, big, red, ar_bank, wave_t, nw, lane);
                     }
                 } else {
-                    view_allreduce<NA, 0, 12, RMAX, RED_SUM>(b12, big, red, wave_t, nw, lane);
+                    view_allreduce<ONEB, NA, 0, 12, RMAX, RED_SUM>(b12, big, red, ar_bank, wave_t, nw, lane);
                 }
                 {
                     const float ie = nr_fast_rcp(big[8]);
@@ -1002,7 +1022,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         }
                     } else if (mo < 4) layer_tile_slice<L_GF1, NT, 0, 2, 0, 1>(W, glane, mo, xq, x1, accf[j]);
                 }
-                view_allreduce<NA, IDLE, 8, RMAX, RED_SUM>(v8, var, red, wave_t, nw, lane);
+                view_allreduce<ONEB, NA, IDLE, 8, RMAX, RED_SUM>(v8, var, red, ar_bank, wave_t, nw, lane);
                 if constexpr (SAVE) {
                     if (wave_t == 1 % nw) {
                         NR_PRAGMA_UNROLL
@@ -1941,6 +1961,45 @@ __global__ void group_scatter_selftest_kernel(const float* __restrict__ x, float
     nr_group_gather4(s4, a, b, c, d);
     nr_group_gather2(nr_group_scatter2(x[l], x[64 + l]), e, f);
     y[l] = a; y[64 + l] = b; y[128 + l] = c; y[192 + l] = d; y[256 + l] = e; y[320 + l] = f; y[384 + l] = s4;
+}
+
+// the two forms of the cross-view all-reduce (nr_device.h block_allreduce / block_allreduce_1b) on the same inputs: one workgroup of nw
+// waves runs the point kernel's own sequence of a tile - 12, 11, 11, 11 rows summed, 2 rows (row 0: maximum), 12, 8 rows summed - twice,
+// 14 calls, so the bank parity of the one-barrier form wraps across an odd count, first in the two-barrier and then in the one-barrier
+// form.  Before each call a wave idles for a wave- and call-dependent time (nr_idle), so that fast waves run a whole all-reduce ahead of
+// slow ones.  x [14 calls][nw][12 rows][64 lanes] -> y [2 forms][14][nw][12][64]: what every wave and lane holds after the call (rows
+// beyond the call's count are left alone).
+constexpr int kArSelfCalls = 14, kArSelfRmax = 12;
+inline size_t allreduce_selftest_smem_bytes(int nw) { return sizeof(float) * 64 * kArSelfRmax * (size_t)(nw + 1 + 2 * nw); }
+template <bool ONEB, int R, int OP>
+__device__ __forceinline__ void ar_selftest_call(const float* __restrict__ x, float* __restrict__ y, int call, float* red, int& bank,
+                                                 int wave, int nw, int lane) {
+    nr_idle(((wave * 5 + call * 3) % 7) * 3);
+    float v[1][R], out[R];
+    for (int r = 0; r < R; ++r) v[0][r] = x[((size_t)(call * nw + wave) * kArSelfRmax + r) * 64 + lane];
+    view_allreduce<ONEB, 1, 0, R, kArSelfRmax, OP>(v, out, red, bank, wave, nw, lane);
+    for (int r = 0; r < R; ++r) y[((size_t)(call * nw + wave) * kArSelfRmax + r) * 64 + lane] = out[r];
+}
+template <bool ONEB>
+__device__ __forceinline__ void ar_selftest_chain(const float* __restrict__ x, float* __restrict__ y, float* red, int wave, int nw, int lane) {
+    int bank = 0;
+    for (int t = 0; t < 2; ++t) {
+        const int c = 7 * t;
+        ar_selftest_call<ONEB, 12, RED_SUM>(x, y, c, red, bank, wave, nw, lane);
+        ar_selftest_call<ONEB, 11, RED_SUM>(x, y, c + 1, red, bank, wave, nw, lane);
+        ar_selftest_call<ONEB, 11, RED_SUM>(x, y, c + 2, red, bank, wave, nw, lane);
+        ar_selftest_call<ONEB, 11, RED_SUM>(x, y, c + 3, red, bank, wave, nw, lane);
+        ar_selftest_call<ONEB, 2, RED_MAX0>(x, y, c + 4, red, bank, wave, nw, lane);
+        ar_selftest_call<ONEB, 12, RED_SUM>(x, y, c + 5, red, bank, wave, nw, lane);
+        ar_selftest_call<ONEB, 8, RED_SUM>(x, y, c + 6, red, bank, wave, nw, lane);
+    }
+}
+__global__ void __launch_bounds__(512) allreduce_selftest_kernel(const float* __restrict__ x, float* __restrict__ y, int nw) {
+    NR_DYNAMIC_SMEM(float, smem);
+    const int lane = threadIdx.x & 63;
+    const int wave = NR_UNIFORM((int)(threadIdx.x >> 6));
+    ar_selftest_chain<false>(x, y, smem, wave, nw, lane);
+    ar_selftest_chain<true>(x, y + (size_t)kArSelfCalls * nw * kArSelfRmax * 64, smem + (size_t)(nw + 1) * kArSelfRmax * 64, wave, nw, lane);
 }
 
 }  // namespace nr

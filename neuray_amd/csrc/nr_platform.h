@@ -315,6 +315,20 @@ template <class T> __device__ __forceinline__ const __attribute__((address_space
 
 // workgroup barrier of the point kernel
 #define NR_BLOCK_SYNC() __syncthreads()
+// every LDS read this wave has issued has LANDED in its registers (s_waitcnt on the LDS counter), and no memory access is moved
+// across this point: the one-barrier all-reduce (nr_device.h) rests its bank re-use on it, not on where the compiler puts its waits
+#ifdef NEURAY_EMU
+#define NR_LDS_LANDED() do {} while (0)
+#else
+#define NR_LDS_LANDED() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+#endif
+// the wave does nothing for a while (self-tests that want the waves of a workgroup out of step): n short sleeps; the emulator
+// hands the processor to the other lanes n times
+#ifdef NEURAY_EMU
+static inline void nr_idle(int n) { for (int i = 0; i < n; ++i) emu::yield_lane(); }
+#else
+__device__ __forceinline__ void nr_idle(int n) { for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(8); }
+#endif
 // orders the LDS traffic of ONE wave (written by some lanes, read by others of the same wave - per-wave scratch, no other wave involved):
 // the LDS executes a wave's instructions in order, so all it takes is that the compiler keeps the order; no s_barrier, no other wave waits
 #ifdef NEURAY_EMU

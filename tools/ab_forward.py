@@ -7,7 +7,8 @@ COARSE pixels / hit probabilities and of the chained fine pixels on N strided ra
 (TEST INFRASTRUCTURE: the oracle is the checker here, computed once).  `build:` entries compile a variant first:
     python tools/ab_forward.py base=neuray_amd/libneuray_hip.so norefine=build:-DNR_FEATURE_RCP_REFINE=0
 (variants are written to _ab/, which is git-ignored).  A path may carry `,nofold`: that library renders with the unfolded
-pack (cfg hip_fold_prob_embed = False; also what a library older than ABI 7 needs); `,x3`: cfg hip_arith = 'x3'."""
+pack (cfg hip_fold_prob_embed = False; also what a library older than ABI 7 needs); `,x3`: cfg hip_arith = 'x3'; `,ar2`: the point
+kernel's cross-view all-reduces in their two-barrier form (NEURAY_POINT_ALLREDUCE=2) from the same library."""
 import argparse
 import json
 import os
@@ -95,6 +96,10 @@ def main():
         path, *opts = path.split(',')
         fold = 'nofold' not in opts
         arith = 'x3' if 'x3' in opts else 'f32'           # `,x3`: NEURAY_ARITH_X3 (three-way split bf16 operands on the K = 32 MFMA)
+        # `,ar2`: NEURAY_POINT_ALLREDUCE=2, the launcher's hook that forces the two-barrier all-reduces (read at every launch)
+        os.environ.pop('NEURAY_POINT_ALLREDUCE', None)
+        if 'ar2' in opts:
+            os.environ['NEURAY_POINT_ALLREDUCE'] = '2'
         if path.startswith('build:'):
             path = build_variant(name, path[6:].split())
         torch.manual_seed(0)
