@@ -99,8 +99,7 @@ int launch_points_form(const nr::PointParams& p, void* stream) {
 #ifndef NR_POINT_GRID
 #define NR_POINT_GRID (256 * 64)
 #endif
-    static const int grid_env = [] { const char* e = getenv("NEURAY_POINT_GRID"); return e ? atoi(e) : 0; }();     // A/B hook (tools/ab_forward.py)
-    int grid = grid_for(npts, 16 * NT, grid_env > 0 ? grid_env : NR_POINT_GRID);
+    int grid = grid_for(npts, 16 * NT, NR_POINT_GRID);
 #ifndef NR_POINT_MIN_TILES
 #define NR_POINT_MIN_TILES 2       // a workgroup's prologue (constants, first weight phase) wants at least this many tiles behind it
 #endif
@@ -192,7 +191,7 @@ void launch_conv2d_x3(const nr::Conv2dX3Params& p, int bands, void* stream) {
     launch_lds(nr::conv2d_x3_kernel<NT, MTW, WC, RELU>, dim3((unsigned)((q + per - 1) / per), (unsigned)(p.cout / 16 / MTW / WC), (unsigned)bands),
                dim3(64 * nr::kC2Waves * WC), smem, stream, p);
 }
-int g_conv2d_nt = 0, g_conv2d_mtw = 0, g_conv2d_tw = 0, g_conv2d_wc = 0;     // NEURAY_CONV2D_NT / _MTW / _TW / _WC: tile-shape overrides of the A/B tools
+int g_conv2d_nt = 0, g_conv2d_mtw = 0;     // NEURAY_CONV2D_NT / _MTW: tile-shape overrides (set by hand; see conv3x3_x3_impl)
 }  // namespace
 
 extern "C" {
@@ -417,7 +416,7 @@ int neuray_conv3x3_x3_pack(const float* w, int cout, int cin, void* wpack, void*
 }
 
 namespace {
-// relu: the entry point with the ReLU epilogue - the default tile shapes only (the NT / MTW overrides of the A/B tools do not apply)
+// relu: the entry point with the ReLU epilogue - the default tile shapes only (the NT / MTW overrides do not apply)
 int conv3x3_x3_impl(bool relu, const float* x, const void* wpack, const float* bias, int n, int cin, int cout, int h, int w, int pad, float* out, void* stream) {
     if (!x || !wpack || !out) return fail("neuray_conv3x3_x3: null pointer");
     if (neuray_conv3x3_x3_pack_bytes(cin, cout) < 0)
@@ -431,11 +430,9 @@ int conv3x3_x3_impl(bool relu, const float* x, const void* wpack, const float* b
         env_read = true;
         if (const char* e = getenv("NEURAY_CONV2D_NT")) g_conv2d_nt = atoi(e);
         if (const char* e = getenv("NEURAY_CONV2D_MTW")) g_conv2d_mtw = atoi(e);
-        if (const char* e = getenv("NEURAY_CONV2D_TW")) g_conv2d_tw = atoi(e);
-        if (const char* e = getenv("NEURAY_CONV2D_WC")) g_conv2d_wc = atoi(e);
     }
     // bands of at most 62 output columns (52-wide rows on 50 / 100 / 200-pixel maps: 2 dropped positions per row, a halo of 106 positions)
-    const int tw_max = g_conv2d_tw > 0 ? g_conv2d_tw : 62;
+    const int tw_max = 62;
     const int bands = (ow + tw_max - 1) / tw_max;
     nr::Conv2dX3Params p;
     p.x = x; p.wpack = (const unsigned*)wpack; p.bias = bias; p.out = out; p.n = n; p.cin = cin; p.cout = cout; p.h = h; p.w = w; p.pad = pad;
@@ -444,25 +441,27 @@ int conv3x3_x3_impl(bool relu, const float* x, const void* wpack, const float* b
     const long long q = (long long)n * (h + 2 * pad) * (p.tw + 2);
     if (q + 1024 >= 0x7fffffffLL) return fail("neuray_conv3x3_x3: n * (h + 2 pad) * (band width + 2) must stay below 2^31");
     // 64 positions x 32 output channels per wave: two workgroups per CU (70 KB of LDS each), the fastest shape on every encoder layer
-    // (profiles/r06_zz5_conv2d_probes.log); the larger tiles stay built for the A/B tool
+    // (profiles/r06_zz5_conv2d_probes.log).  The larger tiles are reached only through NEURAY_CONV2D_NT / _MTW, which no tool sets any more:
+    // they stay because the remaining kernels' code changes without them (profiles/r10_a_device_code_hashes.txt)
     int nt = 4, mtw = 2;
     if (g_conv2d_nt == 4 || g_conv2d_nt == 8) nt = g_conv2d_nt;
     if ((g_conv2d_mtw == 2 || g_conv2d_mtw == 4) && mt % g_conv2d_mtw == 0) mtw = g_conv2d_mtw;
     if ((size_t)nr::conv2d_x3_smem_bytes(nt, p.tw + 2) > 160 * 1024 || nr::conv2d_x3_positions(nt, p.tw + 2) > 64 * nr::conv2d_x3_max_passes(nt))
         return fail("neuray_conv3x3_x3: band of %d columns does not fit the LDS", p.tw);
+    // two channel groups per workgroup where there are at least eight tiles of output channels: -7 % forward / -10 % data gradient at 128
+    // channels, +-3 % at 64 (profiles/r06_zzf_conv2d_wc2.log)
+    const bool wc2 = mt >= 8 && (mt / 2) % 2 == 0 && nr::conv2d_x3_positions(4, p.tw + 2) % 128 == 0;
     if (relu) {
         if ((size_t)nr::conv2d_x3_smem_bytes(4, p.tw + 2) > 160 * 1024 || nr::conv2d_x3_positions(4, p.tw + 2) > 64 * nr::conv2d_x3_max_passes(4))
             return fail("neuray_conv3x3_x3: band of %d columns does not fit the LDS", p.tw);
-        if (mt >= 8 && (mt / 2) % 2 == 0 && nr::conv2d_x3_positions(4, p.tw + 2) % 128 == 0 && g_conv2d_wc != 1) launch_conv2d_x3<4, 2, 2, true>(p, bands, stream);
+        if (wc2) launch_conv2d_x3<4, 2, 2, true>(p, bands, stream);
         else launch_conv2d_x3<4, 2, 1, true>(p, bands, stream);
         return check_launch("neuray_conv3x3_x3_relu");
     }
     if (nt == 8 && mtw == 4) launch_conv2d_x3<8, 4>(p, bands, stream);
     else if (nt == 8) launch_conv2d_x3<8, 2>(p, bands, stream);
     else if (mtw == 4) launch_conv2d_x3<4, 4>(p, bands, stream);
-    // two channel groups per workgroup where there are at least eight tiles of output channels: -7 % forward / -10 % data gradient at 128
-    // channels, +-3 % at 64 (profiles/r06_zzf_conv2d_wc2.log)
-    else if (mt >= 8 && (mt / 2) % 2 == 0 && nr::conv2d_x3_positions(4, p.tw + 2) % 128 == 0 && g_conv2d_wc != 1) launch_conv2d_x3<4, 2, 2>(p, bands, stream);
+    else if (wc2) launch_conv2d_x3<4, 2, 2>(p, bands, stream);
     else launch_conv2d_x3<4, 2>(p, bands, stream);
     return check_launch("neuray_conv3x3_x3");
 }

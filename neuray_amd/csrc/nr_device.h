@@ -57,34 +57,19 @@ __device__ __forceinline__ float norm_inv_depth(float d, float nearp, float farp
     return rn_div(rn_sub(rn_div(-1.0f, d), nearp), rn_sub(farp, nearp));
 }
 
-// Feature-path divisions (they decide no mask and no index).  NR_FEATURE_RCP_REFINE = 1 (default): the hardware reciprocal
-// (v_rcp_f32, 1 ulp) gets one Newton step and a quotient p / d computed as p * RN(1/d) gets one residual correction
-// q' = q + r (p - d q) - two FMAs each, which makes both agree with the correctly rounded division of the reference's op
-// sequence in all but rare halfway cases.  It matters for the texel coordinates: 1 ulp of u / (W - 1) is 1.2e-5 texels on a
-// 200-wide map, i.e. ~2e-5 on a gathered feature of a white-noise map, which the MLP stack carries to the pixel
-// (worst coarse error 1.6e-4 against the 2e-4 gate).  = 0: the round-2 forms, for A/B timing.
-#ifndef NR_FEATURE_RCP_REFINE
-#define NR_FEATURE_RCP_REFINE 1
-#endif
-#ifndef NR_FEATURE_RCP_NEWTON          // the Newton step of 1 / d alone (A/B: the quotient correction is what the texel coordinates need)
-#define NR_FEATURE_RCP_NEWTON NR_FEATURE_RCP_REFINE
-#endif
+// Feature-path divisions (they decide no mask and no index): the hardware reciprocal (v_rcp_f32, 1 ulp) gets one Newton step
+// and a quotient p / d computed as p * RN(1/d) gets one residual correction q' = q + r (p - d q) - two FMAs each, which makes
+// both agree with the correctly rounded division of the reference's op sequence in all but rare halfway cases.  The texel
+// coordinates need it: 1 ulp of u / (W - 1) is 1.2e-5 texels on a 200-wide map, ~2e-5 on a gathered feature of a white-noise
+// map, which the MLP stack carries to the pixel.
 __device__ __forceinline__ float nr_rcp_refined(float d) {
     const float r = nr_fast_rcp(d);
-#if NR_FEATURE_RCP_NEWTON
     return fmaf(fmaf(-d, r, 1.0f), r, r);
-#else
-    return r;
-#endif
 }
 // p / d given r = RN(1 / d)
 __device__ __forceinline__ float nr_div_refined(float p, float d, float r) {
     const float q = p * r;
-#if NR_FEATURE_RCP_REFINE
     return fmaf(fmaf(-d, q, p), r, q);
-#else
-    return q;
-#endif
 }
 // feature-path normalised inverse depth: (-1/d - near') / (far' - near') with inv_range = RN(1 / (far' - near'))
 __device__ __forceinline__ float norm_inv_depth_fast(float d, float nearp, float farp, float inv_range) {
@@ -841,8 +826,10 @@ template <int L, int AR> using LayerPreT = typename layer_pre_of<L, AR>::type;
 template <int L, class WS>
 __device__ __forceinline__ void layer_prefetch(WS W, int lane, LayerPre3<L>& p) {
     static_assert(ws_ar<WS>::value == AR_X3, "a LayerPre3 is filled from an AR_X3 weight source");
-    NR_PRAGMA_UNROLL
-    for (int i = 0; i < LayerPre3<L>::NF; ++i) p.q[i] = frag3_load<L>(W, lane, 0, i / Units3<L>::UPM, i % Units3<L>::UPM);
+    if constexpr (LayerPre3<L>::NF > 0) {       // (a layer without quads: Units3<L>::UPM is 0)
+        NR_PRAGMA_UNROLL
+        for (int i = 0; i < LayerPre3<L>::NF; ++i) p.q[i] = frag3_load<L>(W, lane, 0, i / Units3<L>::UPM, i % Units3<L>::UPM);
+    }
     NR_PRAGMA_UNROLL
     for (int mo = 0; mo < LayerPre3<L>::MT; ++mo) p.b[mo] = wld4(W, (lane >> 4) * 16, (bias_offset(L, AR_X3) + mo * 16) * 4);
     NR_PRAGMA_UNROLL

@@ -217,16 +217,6 @@ __device__ __forceinline__ void view_allreduce(const float (&v)[NA > 0 ? NA : 1]
 
 template <int N> struct SlotCount { static constexpr int value = N; };
 
-#ifndef NR_POINT_SKIP
-#define NR_POINT_SKIP 1        // 0: every view slot runs its layers, masked or not (A/B timing)
-#endif
-#ifndef NR_POINT_TILE_ORDER
-#define NR_POINT_TILE_ORDER 0
-#endif
-#ifndef NR_POINT_TRANSPOSED
-#define NR_POINT_TRANSPOSED 1  // 0: inference tiles are 16 consecutive samples of one ray as well (A/B timing)
-#endif
-
 // Point kernel.  One workgroup = ceil(rfn / VPW) waves x one tile of 16 sample points; wave w processes the reference
 // views [w*VPW, w*VPW + VPW) of the tile ("slots").  The slots of a wave share every weight fragment and give the MFMA
 // pipe independent accumulator chains.
@@ -256,7 +246,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
     NR_DYNAMIC_SMEM(float, smem);
     constexpr int RMAX = point_rmax<NT>();
     constexpr int NS = VPW;
-    constexpr bool SKIP = (NR_POINT_SKIP != 0) && !SAVE && !DBG && VPW == 2;
+    constexpr bool SKIP = !SAVE && !DBG && VPW == 2;
     constexpr bool PKB = pk_form(NR_PK_BLEND, AR), PKV = pk_form(NR_PK_VEC, AR);      // packed or scalar pair sites (nr_platform.h; the ELU's follows the weight source)
     const int lane = threadIdx.x & 63;
     const int wave = NR_UNIFORM((int)(threadIdx.x >> 6));
@@ -304,13 +294,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
     // instead of fetching them into all eight (the grid is a multiple of 8).
     const int bid = (int)(blockIdx.x % 8) * (int)(gridDim.x / 8) + (int)(blockIdx.x / 8);
     int seq0 = 0;                                       // phases entered so far (selects the stage region)
-#ifndef NR_X3_BG_RESIDENT
-#define NR_X3_BG_RESIDENT 1
-#endif
-#ifndef NR_X3_GF_PREFETCH
-#define NR_X3_GF_PREFETCH 1
-#endif
-    constexpr bool BG_RES = AR == AR_X3 && OWN == 1 && (NR_X3_BG_RESIDENT != 0);    // base_fc.0's per-point fragments live in registers (BgResident; 7 or 8 views: one tile per wave, 40 registers)
+    constexpr bool BG_RES = AR == AR_X3 && OWN == 1;    // base_fc.0's per-point fragments live in registers (BgResident; 7 or 8 views: one tile per wave, 40 registers)
     BgResident<OWN> bgres;
     if constexpr (BG_RES) bg_resident_load(W, lane, wave, nw, bgres);
     int n_active = 0, n_slots = 0;                      // slot-skipping statistics of this wave (p.slot_stats)
@@ -319,14 +303,10 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
     // neighbouring texels and leave a view's image together, so more (tile, view) slots are fully masked and skipped (bench scene,
     // coarse pass: 14.1 % instead of 9.2 %) and the 16 columns of a slot share their texel lines.  A point's result does not depend on
     // its tile mates either way.
-    constexpr bool TR = (NR_POINT_TRANSPOSED != 0) && !SAVE && !DBG;
+    constexpr bool TR = !SAVE && !DBG;
     const int nloop = TR ? ((p.rn + 15) / 16) * dn * 16 : npts;
-#ifndef NR_POINT_CHUNK
-#define NR_POINT_CHUNK 1           // consecutive tiles a workgroup walks before it strides on by the grid (A/B: 2, 4, 8)
-#endif
-    constexpr int CH = NR_POINT_CHUNK;
     const int G = (int)gridDim.x;
-    auto tile_base = [&](int it) { return (((it / CH) * G + bid) * CH + (it % CH)) * 16; };
+    auto tile_base = [&](int it) { return (it * G + bid) * 16; };
     if (tile_base(0) < nloop) stage_issue<PH_DIST_M>(wl, W, wave, nw, lane);
     for (int it = 0, base; (base = tile_base(it)) < nloop; ++it, seq0 += phase_count(HAS_VIS)) {
         const bool more = tile_base(it + 1) < nloop;   // another tile follows: its first phase is prefetched
@@ -334,11 +314,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
         // otherwise hipcc treats these loop-invariant loads as hoistable, keeps ~50 fragment registers alive across the
         // whole tile loop and spills them (seen as "spills outside, reloads inside the loop" in -Rpass-missed=regalloc)
         const int glane = lane + nr_opaque_zero();
-#ifndef NR_NO_OPAQUE_WAVE
         const int wave_t = wave + nr_opaque_szero();     // (see nr_opaque_szero)
-#else
-        const int wave_t = wave;
-#endif
         const int gg = glane >> 4;
         const bool dbg_lane = DBG && (gg == 0);
         // the arguments the geometry block and the record stores read, fetched per tile (NR_ARGS_HERE): the query constants alone are
@@ -353,15 +329,9 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
             const float* __restrict__ qc = pt->que_const;
             const float qnearp = qc[24], qfarp = qc[25], qinv = qc[27];
             const int dn = pt->dn, npts = pt->rn * dn;         // (shadow the launch-wide copies: the same values, read here)
-            if constexpr (TR) {
-#if NR_POINT_TILE_ORDER == 1      // sample-major: consecutive tiles are neighbouring ray blocks at one sample index
-                const int tix = base >> 4, nrb = (pt->rn + 15) / 16;
-                smp = tix / nrb;
-                const int rb = tix - smp * nrb;
-#else                             // ray-block-major: consecutive tiles walk along the rays of one block
+            if constexpr (TR) {               // ray-block-major: consecutive tiles walk along the rays of one block
                 const int tix = base >> 4, rb = tix / dn;          // wave-uniform
                 smp = tix - rb * dn;
-#endif
                 ray = rb * 16 + c;
                 pvalid = ray < pt->rn;
                 ray = pvalid ? ray : pt->rn - 1;
@@ -428,19 +398,12 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
             // Measured: +5% whole-job; holding two slots' taps (160 registers) or staggering slot s+1's loads into slot s's
             // blends spills and is slower than this.
             float fray[NA1][8], fimg[NA1][8], rgb[NA1][3];
-#ifdef NR_PROBE_PRE
-            float fm1[NA1][8], fv1[NA1][8], fa1[NA1][8];
-#endif
             if constexpr (NA > 0) {
                 Taps tfs[NA], tcs[NA];
                 NR_PRAGMA_UNROLL
                 for (int s = 0; s < NA; ++s) {
                     tfs[s] = make_taps_fast(pu[s], pv[s], w_m1, h_m1, inv_w_m1, inv_h_m1, p.fw, p.fh, p.fw == p.w && p.fh == p.h);
                     tcs[s] = make_taps_fast(pu[s], pv[s], w_m1, h_m1, inv_w_m1, inv_h_m1, p.w, p.h, true);
-#ifdef NR_PROBE_NO_GATHER      // timing probe (wrong results): every tap of every lane reads texel 0 - what the texture path costs
-                    tfs[s].o00 = tfs[s].o10 = tfs[s].o01 = tfs[s].o11 = 0;
-                    tcs[s].o00 = tcs[s].o10 = tcs[s].o01 = tcs[s].o11 = 0;
-#endif
                 }
                 NR_PRAGMA_UNROLL
                 for (int s = 0; s < NA; ++s) {
@@ -459,21 +422,6 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                     NR_PRAGMA_UNROLL
                     for (int j = 0; j < 3; ++j) NR_KEEP(rgb[s][j]);
                     NR_PIN();
-#ifdef NR_PROBE_PRE            // timing probe (wrong results): the gathers of a map that carries the first layers of the dist heads per texel
-                    {
-                        float4 q1[8], q2[8], q3[8];
-                        issue8(rf_map, goff, soff_f[s] + 4096, tfs[s], q1);
-                        issue8(rf_map, goff, soff_f[s] + 8192, tfs[s], q2);
-                        issue8(rf_map, goff, soff_f[s] + 12288, tfs[s], q3);
-                        NR_PIN();
-                        blend8<PKB>(q1, tfs[s], mask[s], fm1[s]);
-                        blend8<PKB>(q2, tfs[s], mask[s], fv1[s]);
-                        blend8<PKB>(q3, tfs[s], mask[s], fa1[s]);
-                        NR_PRAGMA_UNROLL
-                        for (int k = 0; k < 8; ++k) { NR_KEEP(fm1[s][k]); NR_KEEP(fv1[s][k]); NR_KEEP(fa1[s][k]); }
-                        NR_PIN();
-                    }
-#endif
                 }
             }
             float none[NA1][1];
@@ -495,28 +443,13 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                 const auto W1 = phase_enter<PH_DIST_M, HAS_VIS>(wl, W, seq0, true, wave_t, nw, lane);
                 if constexpr (NA > 0) {
                     LayerPreT<L_DM1, AR> p_dm1; LayerPreT<L_DM2, AR> p_dm2; LayerPreT<L_DV1, AR> p_dv1; VecPre<L_DFIN_M> p_fm;
-#ifdef NR_PROBE_PRE
-                    layer_prefetch<L_DM2>(W1, lane, p_dm2);
-                    NR_PRAGMA_UNROLL
-                    for (int s = 0; s < NA; ++s)
-                        NR_PRAGMA_UNROLL
-                        for (int k = 0; k < 8; ++k) h1[s][k] = elu_s(fm1[s][k]);
-#else
                     layer_prefetch<L_DM1>(W1, lane, p_dm1);
                     layer_fwd<L_DM1, NA, ACT_ELU>(W1, lane, p_dm1, o_fray, none, h1, p_dm2);
-#endif
                     layer_fwd<L_DM2, NA, ACT_ELU>(W1, lane, p_dm2, operand<AR>(h1), none, h2, p_fm);
                     layer_prefetch<L_DV1>(W1, lane, p_dv1);
                     if constexpr (SC) mu_g = softplus(layer_vec_scatter_2x2<L_DFIN_M, PKV>(p_fm, h2, gg));
                     else layer_vec<L_DFIN_M, NA, PKV>(p_fm, h2, fm);
-#ifdef NR_PROBE_PRE
-                    NR_PRAGMA_UNROLL
-                    for (int s = 0; s < NA; ++s)
-                        NR_PRAGMA_UNROLL
-                        for (int k = 0; k < 8; ++k) h1[s][k] = elu_s(fv1[s][k]);
-#else
                     layer_fwd<L_DV1, NA, ACT_ELU>(W1, lane, p_dv1, o_fray, none, h1, last);
-#endif
                 }
                 const auto W2 = phase_enter<PH_DIST_VA, HAS_VIS>(wl, W, seq0, true, wave_t, nw, lane);
                 if constexpr (NA > 0) {
@@ -533,15 +466,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                             s0[s] = softplus(fv[s][0]) + pt->var_bias; s1[s] = softplus(fv[s][1]) + pt->var_bias;
                         }
                     }
-#ifdef NR_PROBE_PRE
-                    layer_prefetch<L_DA2>(W2, lane, p_da2);
-                    NR_PRAGMA_UNROLL
-                    for (int s = 0; s < NA; ++s)
-                        NR_PRAGMA_UNROLL
-                        for (int k = 0; k < 8; ++k) h1[s][k] = elu_s(fa1[s][k]);
-#else
                     layer_fwd<L_DA1, NA, ACT_ELU>(W2, lane, p_da1, o_fray, none, h1, p_da2);
-#endif
                     layer_fwd<L_DA2, NA, ACT_ELU>(W2, lane, p_da2, operand<AR>(h1), none, h2, p_fa);
                     if constexpr (SC) aw_g = sigmoidf(layer_vec_scatter_1x2<L_DFIN_A, 0, PKV>(p_fa, h2));
                     else layer_vec<L_DFIN_A, NA, PKV>(p_fa, h2, fa);
@@ -619,15 +544,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
                         layer_fwd<L_PE1, NA, ACT_RELU>(W3, lane, p_pe1, o_fray, x1, e, p_rd1);
                     } else if (folded) {
                         // prob_embed.2 lives inside neuray_fc.0 / base_fc.0 of this pack: their input is the ReLU output itself
-#ifdef NR_PROBE_PRE
-                        layer_prefetch<L_RD1>(W3, lane, p_rd1);
-                        NR_PRAGMA_UNROLL
-                        for (int s = 0; s < NA; ++s)
-                            NR_PRAGMA_UNROLL
-                            for (int k = 0; k < 8; ++k) e[s][k] = fmaxf(fray[s][k] + x1[s][0], 0.0f);
-#else
                         layer_fwd<L_PE1, NA, ACT_RELU>(W3, lane, p_pe1, fray, x1, e, p_rd1);
-#endif
                     } else {
                         float h[NA][8];
                         LayerPre<L_PE2> p_pe2;
@@ -793,7 +710,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
             }
             // ---------------- base_fc per-view part, vis_fc, vis_fc2, rgb_fc   ibrnet.py:342-349,363-365 ------
             float x[NA1][8], vis2[NA1], z[NA1];
-            constexpr bool GF_PRE = BG_RES && (NR_X3_GF_PREFETCH != 0);
+            constexpr bool GF_PRE = BG_RES;
             float4 gfq[4]; float gfs = 0.0f;
             typename ws_lds<decltype(make_w())>::type W5;
             LayerPreT<L_VF1, AR> p_vf1;
@@ -1073,15 +990,7 @@ __global__ void __launch_bounds__(MAXT, MINW) points_kernel(PointParams p) {
 
         if constexpr (SKIP) {
             const bool a0 = __ballot(mask[0] != 0.0f) != 0ull, a1 = __ballot(mask[1] != 0.0f) != 0ull;
-#ifdef NR_FORCE_NA          // timing probe (wrong results): every wave_t takes the NA-slot body
-#ifdef NR_FORCE_NA_CONST
-            const int na = NR_FORCE_NA;
-#else
-            const int na = NR_FORCE_NA + (p.rn < 0 ? (a0 ? 1 : 0) + (a1 ? 1 : 0) : 0);
-#endif
-#else
             const int na = (a0 ? 1 : 0) + (a1 ? 1 : 0);
-#endif
             n_active += na; n_slots += NS;
             if (na == 2) {
                 tile(SlotCount<2>{});
@@ -1274,11 +1183,7 @@ __global__ void __launch_bounds__(256, 4) rays_kernel(RayParams p) {
                         float den = 0.0f, a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
                         for (int j = 0; j < dn; ++j) {
                             const float4 kj = ld4(ks + j * 16 + hh * 4);
-#ifdef NR_RAY_PROBE_NOSCORE     // timing probe (wrong results): what the QK^T products cost at most
-                            const float s = q[hh * 4] * kj.x;
-#else
                             const float s = fmaf(q[hh * 4 + 3], kj.w, fmaf(q[hh * 4 + 2], kj.z, fmaf(q[hh * 4 + 1], kj.y, q[hh * 4] * kj.x)));
-#endif
                             const float e_ = nr_fast_exp(s - cb[hh]);
                             const float4 vj = ld4(vs + j * 16 + hh * 4);
                             den += e_; a0 = fmaf(e_, vj.x, a0); a1 = fmaf(e_, vj.y, a1); a2 = fmaf(e_, vj.z, a2); a3 = fmaf(e_, vj.w, a3);
@@ -1342,14 +1247,13 @@ __global__ void __launch_bounds__(256, 4) rays_kernel(RayParams p) {
         }
         NR_WAVE_SYNC();         // (K, V, alpha and the transmittance factors are this wave's own LDS)
         // ---- phase 3: compositing.  Transmittance = exclusive prefix product over the samples: a wavefront-shuffle scan (north_star;
-        // round 3).  -DNR_SEQ_COMPOSITE: the round-1/2 form, every lane multiplying its own prefix in torch.cumprod's order.
+        // round 3).
         float cr = 0.0f, cg = 0.0f, cb = 0.0f, cd = 0.0f;
         int cnt = 0;
         for (int ch = 0; ch < nch; ++ch) {
             const int i = ch * 64 + li;
             const bool ok = i < dn;
             float T = 1.0f;
-#ifndef NR_SEQ_COMPOSITE
             // exclusive prefix product over the lanes of the ray's segment in log2 shuffle steps (a second chunk of a > 64-sample ray
             // carries the first chunk's product).  The product associates as a tree, so hit_prob can differ from torch.cumprod's order
             // in the last bit or two (relative 1e-7; the gates are 1e-4); it stays deterministic and independent of batching.  Measured
@@ -1362,9 +1266,6 @@ __global__ void __launch_bounds__(256, 4) rays_kernel(RayParams p) {
                 const float ex = __shfl_up(x, 1);
                 T = (li == 0 ? 1.0f : ex) * carry;
             }
-#else
-            for (int j = 0; j < dn; ++j) { const float tj = tr[j]; T = (j < i) ? T * tj : T; }
-#endif
             const float hp = ok ? al[ok ? i : 0] * T : 0.0f;
             const float* rc = rec + (size_t)(ok ? i : 0) * kPointRec;
             if (ok && rvalid) p.hit_prob[(size_t)ray * dn + i] = hp;

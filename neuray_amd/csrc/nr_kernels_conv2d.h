@@ -27,9 +27,6 @@ constexpr int kC2Waves = 4;
 constexpr int conv2d_x3_positions(int nt, int lw) { return (kC2Waves * nt * 16 + 2 * lw + 2 + 63) / 64 * 64; }      // whole staging passes
 constexpr int conv2d_x3_smem_bytes(int nt, int lw) { return conv2d_x3_positions(nt, lw) * 64 * 3; }
 constexpr int conv2d_x3_max_passes(int nt) { return nt <= 4 ? 7 : 12; }   // staging passes of 64 positions a kernel instance holds in registers
-#ifndef NR_C2_PROBE
-#define NR_C2_PROBE 0                 // timing probes with WRONG results: 1 no staging, 2 no A loads, 3 no B loads, 4 no MFMAs
-#endif
 
 // w [cout][cin][3][3] (fp32) -> wpack.  Lane l = (m = l & 15, g = l >> 4) of tile mt holds, in dword d of part p, the bf16 pair of input channels
 // 32 kb + 8 g + 2 d (+ 1) of output channel 16 mt + m.
@@ -121,7 +118,7 @@ __global__ void __launch_bounds__(64 * kC2Waves * WC) conv2d_x3_kernel(Conv2dX3P
         for (int ps = 0; ps < MAXP; ++ps) {
             if (ps < ps0 || ps >= ps1) continue;                     // (wave-uniform)
             NR_PRAGMA_UNROLL
-            for (int j = 0; j < 8; ++j) v[ps][j] = (NR_C2_PROBE == 1) ? 0.0f : nr_buf_ld1(X, src[ps] >= 0 ? src[ps] + koff + j * plane_b : 0x7ffffff0, 0);
+            for (int j = 0; j < 8; ++j) v[ps][j] = nr_buf_ld1(X, src[ps] >= 0 ? src[ps] + koff + j * plane_b : 0x7ffffff0, 0);
         }
     };
     auto split_store = [&]() NR_LAMBDA_INLINE {
@@ -155,11 +152,7 @@ __global__ void __launch_bounds__(64 * kC2Waves * WC) conv2d_x3_kernel(Conv2dX3P
         const int wb = (((tap * kbn + kb) * mtn + mt0 + mt) * 3) * 1024 + lane * 16;
         NR_PRAGMA_UNROLL
         for (int pt = 0; pt < 3; ++pt) {
-#if NR_C2_PROBE == 2
-            A[pt] = nr_v4u{(unsigned)(wb + mt), (unsigned)pt, 1u, 2u};
-#else
             A[pt] = nr_buf_ld4u(W, s < steps ? wb + pt * 1024 : 0x7ffffff0, 0);
-#endif
         }
     };
     const int rd0 = (wave * NT * 16 + c) * 64 + g * 16;            // the wave's tile 0, tap (0, 0)
@@ -170,11 +163,7 @@ __global__ void __launch_bounds__(64 * kC2Waves * WC) conv2d_x3_kernel(Conv2dX3P
         for (int t = 0; t < NT; ++t)
             NR_PRAGMA_UNROLL
             for (int pt = 0; pt < 3; ++pt) {
-#if NR_C2_PROBE == 3
-                B[t][pt] = nr_v4u{(unsigned)(t + tap), (unsigned)pt, 1u, 2u};
-#else
                 B[t][pt] = *reinterpret_cast<const nr_v4u*>(rb + t * 1024 + pt * part_bytes);
-#endif
             }
     };
 
@@ -191,11 +180,7 @@ __global__ void __launch_bounds__(64 * kC2Waves * WC) conv2d_x3_kernel(Conv2dX3P
         for (int pr = 0; pr < 6; ++pr)
             NR_PRAGMA_UNROLL
             for (int t = 0; t < NT; ++t) {
-#if NR_C2_PROBE == 4
-                acc[t][mt][pr & 3] += __builtin_bit_cast(float, A[WI[pr]][0] ^ B[t][XJ[pr]][1]);
-#else
                 acc[t][mt] = nr_mfma16x32_bf16(A[WI[pr]], B[t][XJ[pr]], acc[t][mt]);
-#endif
             }
     };
 #pragma unroll 1

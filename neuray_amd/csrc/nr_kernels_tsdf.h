@@ -248,11 +248,7 @@ __global__ void __launch_bounds__(kTsdfTileX * kTsdfTileY) surface_emit_kernel(S
 // ---- ray casting (the contract is at the head of this file) ----
 constexpr int kTsdfBlock = 8;                         // cells per block and axis
 constexpr int kRaycastMaxK = 1 << 22;
-#ifdef NR_RAYCAST_ROWS                                // a wave covers 64 x 1 pixels (the alternative measured in DESIGN.md 4.22)
-constexpr int kRaycastWaveX = 64, kRaycastWaveY = 1, kRaycastWavesX = 1, kRaycastWavesY = 4;
-#else                                                 // a wave covers 8 x 8 pixels, a workgroup 2 x 2 of them
-constexpr int kRaycastWaveX = 8, kRaycastWaveY = 8, kRaycastWavesX = 2, kRaycastWavesY = 2;
-#endif
+constexpr int kRaycastWaveX = 8, kRaycastWaveY = 8, kRaycastWavesX = 2, kRaycastWavesY = 2;      // a wave covers 8 x 8 pixels, a workgroup 2 x 2 of them
 constexpr int kRaycastTileX = kRaycastWaveX * kRaycastWavesX, kRaycastTileY = kRaycastWaveY * kRaycastWavesY;
 
 struct SurfaceBlocksParams {

@@ -5,7 +5,7 @@
 For every library: rays/s, point-kernel ms per launch (HIP events of the engine), and - with --parity N - the error of the
 COARSE pixels / hit probabilities and of the chained fine pixels on N strided rays of the image against the numpy oracle
 (TEST INFRASTRUCTURE: the oracle is the checker here, computed once).  `build:` entries compile a variant first:
-    python tools/ab_forward.py base=neuray_amd/libneuray_hip.so norefine=build:-DNR_FEATURE_RCP_REFINE=0
+    python tools/ab_forward.py base=neuray_amd/libneuray_hip.so minw2=build:-DNR_POINT_MINW=2
 (variants are written to _ab/, which is git-ignored).  A path may carry `,nofold`: that library renders with the unfolded
 pack (cfg hip_fold_prob_embed = False; also what a library older than ABI 7 needs); `,x3`: cfg hip_arith = 'x3'; `,ar2`: the point
 kernel's cross-view all-reduces in their two-barrier form (NEURAY_POINT_ALLREDUCE=2) from the same library."""
