@@ -870,6 +870,75 @@ typedef struct NeurayTsdfRaycastArgs {
 } NeurayTsdfRaycastArgs;
 int neuray_tsdf_raycast(const NeurayTsdfRaycastArgs* args, void* stream);
 
+/* ---- augmentation of the procedural stream (neuray_amd/procedural.py augment_numpy; added within ABI 11: everything above
+ * is unchanged).  The data-dependent steps of the reference's training sample for a `gso` scene - depth-range augmentation, depth noise,
+ * consistent depth ranges, foreground / background ray sampling - on depth maps and masks that live on the device.  The fp32 library only
+ * (the bf16-operand variants return an error).  No float atomics; the results are bitwise reproducible.  n <= 65535, h * w < 2^31.
+ * Random numbers: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85), key = (key0, key1), counter =
+ * (pixel y * w + x, view, purpose, 0), u = float(word >> 8) * 2^-24; purposes 0 / 1: the local noise of the large / small offset region (word
+ * 0), 2: the global noise (word 0), 3: the ray selection (words 0 and 1).  Symmetric noise of amplitude a: ((2 u - 1) a) L.
+ * neuray_augment_stats, per view over mask > 0: stats [n][NEURAY_AUGMENT_STATS] int32 = count, xmin, xmax, ymin, ymax, the float bits of the
+ *   min and of the max depth over the pixels that are also valid (1e-3 < d < 1e4), 0; row_counts [n][h] = the foreground pixels of every row.
+ *   An empty mask: count 0, xmin = w, xmax = -1, ymin = h, ymax = -1; no valid depth: min = +inf, max = -inf.  row_part [n][h][4]: workspace.
+ * neuray_augment_depth, with uniform(lo, hi, u) = lo + (hi - lo) u and host_dev [NEURAY_AUGMENT_HOST (1 + rfn)] floats that the host drew:
+ *     head: shrink on, u_far, u_near, widen on, u_0, u_1, consistent on, 0, then the large region's region min, region max, offset min,
+ *     offset max, local amplitude, 0 0 0; working view r: per region (large, small) on, u_centre, u_lx, u_ly, u_offset, negative; global noise on; 0 0 0
+ *   1. ranges: with shrink on, over the views with a valid depth, far_ratio = max (1.1 dmax) / far, near_ratio = max near / (0.9 dmin);
+ *      far_ratio < 1: far *= uniform(far_ratio, 1, u_far); near_ratio < 1: near /= uniform(near_ratio, 1, u_near); with widen on:
+ *      near *= 1 - uniform(0.025, 0.1, u_0), far *= 1 + uniform(0.025, 0.1, u_1) -> range_aug [n][2].
+ *   2. plan [rfn][2][NEURAY_AUGMENT_PLAN] of the working views [view0, view0 + rfn), L = far - near of range_aug: on (the host's flag and
+ *      count > 0), cx, cy (the foreground pixel of row-major rank min(int(u_centre float(count)), count - 1)), lx, ly = uniform(region min,
+ *      region max, u) (xmax - xmin, ymax - ymin), the offset uniform(offset min, offset max, u_offset) L (negated with `negative`), the local
+ *      amplitude, L; the small region's literals: 0.1, 0.2, 0.01, 0.05, 0.005.  depth_aug [rfn][h][w] = depth, plus per region that is on, where
+ *      mask > 0 and |x - cx| < lx and |y - cy| < ly: noise(amplitude, L) + offset, plus with global noise on, everywhere: noise(0.005, L).
+ *   3. with consistent on: max_len = max (far - near); near' = max(near - (max_len - (far - near)) / 2, 0.5 near), far' = near' + max_len
+ *      -> range_out [n][2] (else range_out = range_aug).
+ * neuray_sample_coords: pixel p of the view's mask [h][w] carries the composites (word0 << 32) | p and (word1 << 32) | p.  Stage 0 takes the
+ *   min(want_fg, foreground) foreground pixels with the smallest first composite, stage 1 the ray_num - that many pixels with the smallest
+ *   second composite among all pixels stage 0 left.  coords [ray_num][2] float (x, y): stage 0's picks, then stage 1's, each in row-major
+ *   order.  1 <= ray_num <= h * w, 0 <= want_fg <= ray_num.  keys [2][h * w] uint32, taken [h * w] bytes and work
+ *   [NEURAY_SAMPLE_COORDS_WORK] 64-bit words are workspace (no need to clear them). */
+#define NEURAY_AUGMENT_STATS 8
+#define NEURAY_AUGMENT_PLAN 8
+#define NEURAY_AUGMENT_HOST 16
+#define NEURAY_SAMPLE_COORDS_WORK 16416
+typedef struct NeurayAugmentStatsArgs {
+    const unsigned char* mask_dev;     /* [n][h][w] */
+    const float* depth_dev;            /* [n][h][w] */
+    int* row_counts_dev;               /* [n][h] */
+    int* row_part_dev;                 /* [n][h][4] */
+    int* stats_dev;                    /* [n][NEURAY_AUGMENT_STATS] */
+    int n, h, w, reserved;
+} NeurayAugmentStatsArgs;
+int neuray_augment_stats(const NeurayAugmentStatsArgs* args, void* stream);
+
+typedef struct NeurayAugmentDepthArgs {
+    const float* depth_dev;            /* [n][h][w] */
+    const unsigned char* mask_dev;     /* [n][h][w] */
+    const float* range_in_dev;         /* [n][2] near, far */
+    const int* stats_dev;              /* the two outputs of neuray_augment_stats */
+    const int* row_counts_dev;
+    const float* host_dev;
+    float* range_aug_dev;              /* [n][2] */
+    float* range_out_dev;              /* [n][2] */
+    float* plan_dev;                   /* [rfn][2][NEURAY_AUGMENT_PLAN] */
+    float* depth_aug_dev;              /* [rfn][h][w] */
+    int n, h, w, view0, rfn, reserved;
+    unsigned key0, key1;
+} NeurayAugmentDepthArgs;
+int neuray_augment_depth(const NeurayAugmentDepthArgs* args, void* stream);
+
+typedef struct NeuraySampleCoordsArgs {
+    const unsigned char* mask_dev;     /* [h][w] */
+    unsigned* keys_dev;
+    unsigned char* taken_dev;
+    unsigned long long* work_dev;
+    float* coords_dev;                 /* [ray_num][2] */
+    int h, w, ray_num, want_fg, view, reserved;
+    unsigned key0, key1;
+} NeuraySampleCoordsArgs;
+int neuray_sample_coords(const NeuraySampleCoordsArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,7 +144,24 @@ class NeurayTsdfRaycastArgs(C.Structure):
         [(n, C.c_int) for n in ('nx', 'ny', 'nz', 'n', 'h', 'w', 'reserved', 'reserved2')]
 
 
-TSDF_BLOCK = 8                 # cells per block and axis (neuray_surface_blocks)
+class NeurayAugmentStatsArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('mask_dev', 'depth_dev', 'row_counts_dev', 'row_part_dev', 'stats_dev')] + \
+        [(n, C.c_int) for n in ('n', 'h', 'w', 'reserved')]
+
+
+class NeurayAugmentDepthArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('depth_dev', 'mask_dev', 'range_in_dev', 'stats_dev', 'row_counts_dev', 'host_dev', 'range_aug_dev',
+                                          'range_out_dev', 'plan_dev', 'depth_aug_dev')] + \
+        [(n, C.c_int) for n in ('n', 'h', 'w', 'view0', 'rfn', 'reserved')] + [('key0', C.c_uint), ('key1', C.c_uint)]
+
+
+class NeuraySampleCoordsArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('mask_dev', 'keys_dev', 'taken_dev', 'work_dev', 'coords_dev')] + \
+        [(n, C.c_int) for n in ('h', 'w', 'ray_num', 'want_fg', 'view', 'reserved')] + [('key0', C.c_uint), ('key1', C.c_uint)]
+
+
+AUGMENT_STATS, AUGMENT_PLAN, AUGMENT_HOST, SAMPLE_COORDS_WORK = 8, 8, 16, 16416   # include/neuray_hip.h NEURAY_AUGMENT_*, NEURAY_SAMPLE_COORDS_WORK
+TSDF_BLOCK = 8                # cells per block and axis (neuray_surface_blocks)
 TSDF_MAX_POINTS = 1 << 30      # nx * ny * nz of a volume (include/neuray_hip.h)
 FUSE_MAX_SRC = 16              # include/neuray_hip.h NEURAY_FUSE_MAX_SRC
 PROC_HEADER, PROC_PRIM, PROC_MAX_PRIMS = 16, 48, 32   # the scene array of neuray_procedural_render (include/neuray_hip.h NEURAY_PROC_*)
@@ -294,6 +311,10 @@ SYMBOLS = {
     'neuray_surface_blocks': (C.c_int, [C.POINTER(NeuraySurfaceBlocksArgs), C.c_void_p]),
     'neuray_tsdf_raycast': (C.c_int, [C.POINTER(NeurayTsdfRaycastArgs), C.c_void_p]),
     'neuray_inorm_backward_det': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 7),
+    # augmentation of the procedural stream
+    'neuray_augment_stats': (C.c_int, [C.POINTER(NeurayAugmentStatsArgs), C.c_void_p]),
+    'neuray_augment_depth': (C.c_int, [C.POINTER(NeurayAugmentDepthArgs), C.c_void_p]),
+    'neuray_sample_coords': (C.c_int, [C.POINTER(NeuraySampleCoordsArgs), C.c_void_p]),
 }
 
 

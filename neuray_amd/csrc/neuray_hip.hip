@@ -22,6 +22,7 @@
 #include "nr_kernels_vis.h"         // (fp32 MFMA only: the bf16-operand builds leave the visibility entries returning an error)
 #include "nr_kernels_fuse.h"        // (the fp32 library only, like the visibility entries)
 #include "nr_kernels_tsdf.h"        // (likewise)
+#include "nr_kernels_aug.h"         // (likewise)
 #endif
 #include "nr_pack.h"
 #include "../../include/neuray_hip.h"
@@ -1422,6 +1423,93 @@ int neuray_procedural_render(const NeurayProceduralArgs* a, void* stream) {
     const dim3 grid((unsigned)((a->w + nr::kProcTileX - 1) / nr::kProcTileX), (unsigned)((a->h + nr::kProcTileY - 1) / nr::kProcTileY), (unsigned)a->n);
     NR_LAUNCH(nr::procedural_render_kernel, grid, dim3(nr::kProcTileX * nr::kProcTileY), 0, stream, p);
     return check_launch("neuray_procedural_render");
+}
+
+// ---- augmentation of the procedural stream ----
+#ifndef NR_BF16_QUADS
+static_assert(NEURAY_AUGMENT_STATS == nr::kAugStats && NEURAY_AUGMENT_PLAN == nr::kAugPlan && NEURAY_AUGMENT_HOST == nr::kAugHost, "abi");
+static_assert(NEURAY_SAMPLE_COORDS_WORK == nr::kSampleWorkWords, "abi");
+static int augment_common(const char* who, int n, int h, int w) {
+    if (n < 1 || h < 1 || w < 1) return fail("%s: bad size n=%d h=%d w=%d", who, n, h, w);
+    if (n > 65535) return fail("%s: n=%d too large for one call", who, n);
+    if ((long long)h * w > 0x7fffffffLL) return fail("%s: h*w too large (a pixel index is an int)", who);
+    return 0;
+}
+#endif
+
+int neuray_augment_stats(const NeurayAugmentStatsArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_augment_stats: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_augment_stats: null args");
+    if (int rc = augment_common("neuray_augment_stats", a->n, a->h, a->w)) return rc;
+    if (!a->mask_dev || !a->depth_dev || !a->row_counts_dev || !a->row_part_dev || !a->stats_dev) return fail("neuray_augment_stats: mask / depth / row_counts / row_part / stats missing");
+    nr::AugStatsParams p;
+    p.mask = a->mask_dev; p.depth = a->depth_dev; p.row_counts = a->row_counts_dev; p.row_part = a->row_part_dev; p.stats = a->stats_dev;
+    p.n = a->n; p.h = a->h; p.w = a->w;
+    NR_LAUNCH(nr::augment_row_stats_kernel, dim3((unsigned)a->h, (unsigned)a->n), dim3(nr::kAugBlock), 0, stream, p);
+    NR_LAUNCH(nr::augment_view_stats_kernel, dim3((unsigned)a->n), dim3(nr::kAugBlock), 0, stream, p);
+    return check_launch("neuray_augment_stats");
+#endif
+}
+
+int neuray_augment_depth(const NeurayAugmentDepthArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_augment_depth: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_augment_depth: null args");
+    if (int rc = augment_common("neuray_augment_depth", a->n, a->h, a->w)) return rc;
+    if (a->rfn < 0 || a->view0 < 0 || a->view0 + a->rfn > a->n) return fail("neuray_augment_depth: working views [%d,%d) outside [0,%d)", a->view0, a->view0 + a->rfn, a->n);
+    if (!a->depth_dev || !a->mask_dev || !a->range_in_dev || !a->stats_dev || !a->row_counts_dev || !a->host_dev) return fail("neuray_augment_depth: depth / mask / range_in / stats / row_counts / host missing");
+    if (!a->range_aug_dev || !a->range_out_dev || (a->rfn > 0 && (!a->plan_dev || !a->depth_aug_dev))) return fail("neuray_augment_depth: range_aug / range_out / plan / depth_aug missing");
+    nr::AugDepthParams p;
+    p.depth = a->depth_dev; p.mask = a->mask_dev; p.range_in = a->range_in_dev; p.stats = a->stats_dev; p.row_counts = a->row_counts_dev;
+    p.host = a->host_dev; p.range_aug = a->range_aug_dev; p.range_out = a->range_out_dev; p.plan = a->plan_dev; p.depth_aug = a->depth_aug_dev;
+    p.n = a->n; p.h = a->h; p.w = a->w; p.view0 = a->view0; p.rfn = a->rfn; p.key0 = a->key0; p.key1 = a->key1;
+    NR_LAUNCH(nr::augment_plan_kernel, dim3((unsigned)(a->rfn > 0 ? a->rfn : 1)), dim3(64), 0, stream, p);
+    if (a->rfn > 0) {
+        const long long plane = (long long)a->h * a->w;
+        NR_LAUNCH(nr::augment_apply_kernel, dim3((unsigned)((plane + nr::kAugBlock - 1) / nr::kAugBlock), (unsigned)a->rfn), dim3(nr::kAugBlock), 0, stream, p);
+    }
+    return check_launch("neuray_augment_depth");
+#endif
+}
+
+int neuray_sample_coords(const NeuraySampleCoordsArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_sample_coords: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_sample_coords: null args");
+    if (int rc = augment_common("neuray_sample_coords", 1, a->h, a->w)) return rc;
+    const long long N = (long long)a->h * a->w;
+    if (a->ray_num < 1 || a->ray_num > N) return fail("neuray_sample_coords: ray_num=%d outside [1, h*w=%lld]", a->ray_num, N);
+    if (a->want_fg < 0 || a->want_fg > a->ray_num) return fail("neuray_sample_coords: want_fg=%d outside [0, ray_num=%d]", a->want_fg, a->ray_num);
+    if (!a->mask_dev || !a->keys_dev || !a->taken_dev || !a->work_dev || !a->coords_dev) return fail("neuray_sample_coords: mask / keys / taken / work / coords missing");
+    nr::SampleParams p;
+    p.mask = a->mask_dev; p.keys = a->keys_dev; p.taken = a->taken_dev; p.work = a->work_dev; p.coords = a->coords_dev;
+    p.N = (int)N; p.w = a->w; p.ray_num = a->ray_num; p.want_fg = a->want_fg; p.view = a->view; p.key0 = a->key0; p.key1 = a->key1;
+    // every workgroup owns `chunk` consecutive pixels (a multiple of 256, at least 1024), at most kSampleMaxBlocks workgroups
+    long long chunk = (N + nr::kSampleMaxBlocks - 1) / nr::kSampleMaxBlocks;
+    chunk = (chunk + nr::kAugBlock - 1) / nr::kAugBlock * nr::kAugBlock;
+    if (chunk < 4 * nr::kAugBlock) chunk = 4 * nr::kAugBlock;
+    p.chunk = (int)chunk; p.nblocks = (int)((N + chunk - 1) / chunk);
+    p.stage = 0; p.pass = 0;
+    const dim3 grid((unsigned)p.nblocks), block(nr::kAugBlock);
+    NR_LAUNCH(nr::sample_keys_kernel, grid, block, 0, stream, p);
+    for (int stage = 0; stage < 2; ++stage) {
+        p.stage = stage;
+        for (int pass = 0; pass < nr::kSamplePasses; ++pass) {
+            p.pass = pass;
+            NR_LAUNCH(nr::sample_hist_kernel, grid, block, 0, stream, p);
+        }
+        NR_LAUNCH(nr::sample_count_kernel, grid, block, 0, stream, p);
+        NR_LAUNCH(nr::sample_emit_kernel, grid, block, 0, stream, p);
+    }
+    return check_launch("neuray_sample_coords");
+#endif
 }
 
 // ---- geometry export ----

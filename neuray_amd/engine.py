@@ -996,6 +996,81 @@ class RenderEngine:
         self._event_done(ev, 'procedural', n * int(h) * int(w))
         return out
 
+    # ---- augmentation of the procedural stream (neuray_amd/procedural.py) ----
+    def _augment_maps(self, what, mask, depth=None):
+        if self.variant != 'fp32':
+            raise NotImplementedError("neuray_amd: %s lives in the fp32 library (variant=%r)" % (what, self.variant))
+        mask = torch.as_tensor(mask).detach().to(self.device)
+        if mask.dtype != torch.uint8:
+            mask = (mask > 0).to(torch.uint8)
+        mask = mask.reshape(-1, *mask.shape[-2:]).contiguous()
+        if depth is None:
+            return mask
+        depth = self._f32(torch.as_tensor(depth))
+        depth = depth.reshape(-1, *depth.shape[-2:])
+        assert depth.shape == mask.shape, "depth %s for mask %s" % (tuple(depth.shape), tuple(mask.shape))
+        return mask, depth
+
+    def augment_stats(self, mask, depth):
+        """Per view over mask > 0 (include/neuray_hip.h, neuray_augment_stats): mask [n,h,w] (uint8, or anything compared with 0), depth
+        [n,h,w] -> dict of device tensors: stats [n,8] int32 (the kernel's record), and as views of it count [n], bbox [n,4] (xmin, xmax,
+        ymin, ymax), depth_min / depth_max [n] float32 (over the pixels with 1e-3 < d < 1e4); row_counts [n,h] int32.  No host
+        synchronisation."""
+        mask, depth = self._augment_maps('augment_stats', mask, depth)
+        n, h, w = mask.shape
+        stats, rows = self.empty(n, _lib.AUGMENT_STATS, dtype=torch.int32), self.empty(n, h, dtype=torch.int32)
+        part = self.empty(n, h, 4, dtype=torch.int32)
+        a = _lib.NeurayAugmentStatsArgs(mask.data_ptr(), depth.data_ptr(), rows.data_ptr(), part.data_ptr(), stats.data_ptr(), n, h, w, 0)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_augment_stats(C.byref(a), self._stream()))
+        self._event_done(ev, 'augment_stats', n * h * w)
+        extrema = stats[:, 5:7].contiguous().view(torch.float32)
+        return {'stats': stats, 'count': stats[:, 0], 'bbox': stats[:, 1:5], 'depth_min': extrema[:, 0], 'depth_max': extrema[:, 1],
+                'row_counts': rows}
+
+    def augment_depth(self, depth, mask, depth_range, stats, host, key, view0, rfn):
+        """Range augmentation, depth noise and consistent ranges (neuray_augment_depth; the formulas: procedural.augment_numpy).
+        depth / mask [n,h,w], depth_range [n,2], stats: augment_stats' result for the same maps, host: the float32 array
+        procedural.augment_host_numbers draws ([16 (1 + rfn)]), key: (seed, batch index), the working views are [view0, view0 + rfn)
+        -> dict(depth_range_aug [n,2], depth_range [n,2], plan [rfn,2,8], depth_aug [rfn,h,w]).  No host synchronisation."""
+        mask, depth = self._augment_maps('augment_depth', mask, depth)
+        n, h, w = mask.shape
+        rng_in = self._f32(torch.as_tensor(depth_range)).reshape(-1, 2)
+        host = self._f32(torch.as_tensor(host)).reshape(-1)
+        view0, rfn = int(view0), int(rfn)
+        assert rng_in.shape[0] == n and host.numel() >= _lib.AUGMENT_HOST * (1 + max(rfn, 0))
+        assert stats['stats'].shape == (n, _lib.AUGMENT_STATS) and stats['row_counts'].shape == (n, h)
+        out = {'depth_range_aug': self.empty(n, 2), 'depth_range': self.empty(n, 2), 'plan': self.empty(max(rfn, 0), 2, _lib.AUGMENT_PLAN),
+               'depth_aug': self.empty(max(rfn, 0), h, w)}
+        a = _lib.NeurayAugmentDepthArgs(depth.data_ptr(), mask.data_ptr(), rng_in.data_ptr(), stats['stats'].data_ptr(),
+                                        stats['row_counts'].data_ptr(), host.data_ptr(), out['depth_range_aug'].data_ptr(),
+                                        out['depth_range'].data_ptr(), out['plan'].data_ptr(), out['depth_aug'].data_ptr(), n, h, w, view0, rfn, 0,
+                                        int(key[0]) & 0xffffffff, int(key[1]) & 0xffffffff)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_augment_depth(C.byref(a), self._stream()))
+        self._event_done(ev, 'augment_depth', max(rfn, 0) * h * w)
+        return out
+
+    def sample_coords(self, mask, ray_num, foreground_ratio, key, view=0):
+        """get_coords_mask without a shuffle (neuray_sample_coords): mask [h,w] -> coords [1,ray_num,2] float32 (x, y):
+        int(ray_num * foreground_ratio) foreground pixels (all of them where there are fewer), then the rest from every pixel not yet
+        picked, each part in row-major order.  key: (seed, batch index); view: the view's index in the Philox counter.  ray_num > h * w
+        is an error.  No host synchronisation."""
+        mask = self._augment_maps('sample_coords', mask)
+        assert mask.shape[0] == 1, "one mask [h,w]: %s" % (tuple(mask.shape),)
+        _, h, w = mask.shape
+        ray_num = int(ray_num)
+        want_fg = int(ray_num * foreground_ratio)
+        coords = self.empty(1, max(ray_num, 0), 2)
+        keys, taken = self.empty(2, h * w, dtype=torch.int32), self.empty(h * w, dtype=torch.uint8)
+        work = self.empty(_lib.SAMPLE_COORDS_WORK, dtype=torch.int64)
+        a = _lib.NeuraySampleCoordsArgs(mask.data_ptr(), keys.data_ptr(), taken.data_ptr(), work.data_ptr(), coords.data_ptr(), h, w, ray_num,
+                                        want_fg, int(view), 0, int(key[0]) & 0xffffffff, int(key[1]) & 0xffffffff)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_sample_coords(C.byref(a), self._stream()))
+        self._event_done(ev, 'sample_coords', h * w)
+        return coords
+
     # ---- geometry export (neuray_amd/geometry.py, DESIGN.md 4.20) ----
     def _fuse_inputs(self, depth, poses, Ks, nn_ids, Ks_inv):
         if self.variant != 'fp32':

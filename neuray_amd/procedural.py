@@ -372,6 +372,187 @@ class ProceduralDatabase(BaseDatabase):
         return [xs.min(), ys.min(), xs.max() - xs.min() + 1, ys.max() - ys.min() + 1]
 
 
+# ---- augmentation of a training sample -----------------------------------------------------------------------------------
+# What the reference's GeneralRendererDataset.__getitem__ does to a `gso` sample (objects, masks, exact depth), in its order: the depth
+# ranges of all views are shrunk towards the masked depth and widened; the depth maps the init net sees are corrupted (two offset regions
+# and a global noise per working view, scaled by the view's augmented range) while true_depth keeps the exact map; the ranges are made
+# consistent; half of the rays are drawn from the query view's foreground.  The host draws the numbers that do not depend on device data
+# (augment_host_numbers); per-pixel randomness is Philox4x32-10, key = (stream seed, batch index), counter = (y * w + x, view, purpose, 0),
+# purposes 0 / 1: the local noise of the large / small region, 2: the global noise, 3: the ray selection.  augment_numpy and
+# sample_coords_numpy are the formulas (the reference of the tests, the path of a machine without a GPU); csrc/nr_kernels_aug.h through
+# RenderEngine.augment_stats / augment_depth / sample_coords evaluates them in fp32 on the device.
+AUGMENT_DEFAULTS = {
+    'aug_gso_shrink_range_prob': 0.5,
+    'aug_use_depth_offset': True, 'aug_depth_offset_prob': 0.25, 'aug_depth_offset_region_min': 0.05, 'aug_depth_offset_region_max': 0.1,
+    'aug_depth_offset_min': 0.5, 'aug_depth_offset_max': 1.0, 'aug_depth_offset_local': 0.1,
+    'aug_use_depth_small_offset': True, 'aug_depth_small_offset_prob': 0.5,
+    'aug_use_global_noise': True, 'aug_global_noise_prob': 0.5,
+    'foreground_ratio': 0.5, 'use_consistent_depth_range': True,
+}
+AUG_HOST = 16                                        # floats of the host array's head and of every working view (include/neuray_hip.h)
+_SMALL_REGION = (0.1, 0.2, 0.01, 0.05, 0.005)        # region min / max, offset min / max, local amplitude: the reference's literals
+_M32 = 0xffffffff
+
+
+def augment_config(augment):
+    """None / False -> None (no augmentation); True -> the reference's defaults; a dict overrides keys of AUGMENT_DEFAULTS"""
+    if augment is None or augment is False:
+        return None
+    cfg = dict(AUGMENT_DEFAULTS)
+    if augment is not True:
+        unknown = set(augment) - set(cfg)
+        if unknown:
+            raise KeyError("neuray_amd.procedural: unknown augmentation keys %s" % sorted(unknown))
+        cfg.update(augment)
+    return cfg
+
+
+def philox4x32(counter, key, rounds=10):
+    """Philox4x32-10 (Random123): counter [..., 4] and key (k0, k1) as uint32 -> [..., 4] uint32"""
+    c = np.asarray(counter, np.uint64)
+    c = [c[..., i] for i in range(4)]
+    k0, k1 = int(key[0]) & _M32, int(key[1]) & _M32
+    m = np.uint64(_M32)
+    for _ in range(rounds):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & m, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & m]
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return np.stack(c, -1).astype(np.uint32)
+
+
+def _pixel_words(h, w, view, purpose, key):
+    """the Philox block of every pixel of a view -> [h * w, 4] uint32"""
+    ctr = np.zeros((h * w, 4), np.uint64)
+    ctr[:, 0], ctr[:, 1], ctr[:, 2] = np.arange(h * w), view, purpose
+    return philox4x32(ctr, key)
+
+
+def augment_host_numbers(rng, rfn, cfg):
+    """The numbers of one batch that do not depend on device data, drawn from `rng` in a fixed order -> float32 [AUG_HOST (1 + rfn)]
+    (the layout: include/neuray_hip.h, neuray_augment_depth).  A uniform is randint(0, 2^24) / 2^24: exact in float32, never 1."""
+    def u():
+        return rng.randint(0, 2 ** 24) / 2.0 ** 24
+    out = np.zeros((1 + rfn, AUG_HOST), np.float32)
+    out[0, :7] = [u() < cfg['aug_gso_shrink_range_prob'], u(), u(), u() < 0.8, u(), u(), bool(cfg['use_consistent_depth_range'])]
+    out[0, 8:13] = [cfg['aug_depth_offset_region_min'], cfg['aug_depth_offset_region_max'], cfg['aug_depth_offset_min'],
+                    cfg['aug_depth_offset_max'], cfg['aug_depth_offset_local']]
+    for r in range(rfn):
+        for k, (use, prob) in enumerate((('aug_use_depth_offset', 'aug_depth_offset_prob'), ('aug_use_depth_small_offset', 'aug_depth_small_offset_prob'))):
+            on = u() < cfg[prob]
+            out[1 + r, 6 * k: 6 * k + 6] = [bool(cfg[use]) and on, u(), u(), u(), u(), u() < 0.5]
+        on = u() < cfg['aug_global_noise_prob']
+        out[1 + r, 12] = bool(cfg['aug_use_global_noise']) and on
+    return out.reshape(-1)
+
+
+def stats_numpy(mask, depth):
+    """per view over mask > 0 -> dict(count [n], bbox [n,4] (xmin, xmax, ymin, ymax), depth_min / depth_max [n] float32 over the pixels
+    with 1e-3 < d < 1e4, row_counts [n,h]); an empty mask: count 0, bbox (w, -1, h, -1); no valid depth: +inf / -inf"""
+    mask, depth = np.asarray(mask), np.asarray(depth, np.float32)
+    n, h, w = mask.shape
+    out = {'count': np.zeros(n, np.int32), 'bbox': np.zeros((n, 4), np.int32), 'depth_min': np.full(n, np.inf, np.float32),
+           'depth_max': np.full(n, -np.inf, np.float32), 'row_counts': (mask > 0).sum(2).astype(np.int32)}
+    for v in range(n):
+        ys, xs = np.nonzero(mask[v] > 0)
+        out['count'][v] = ys.size
+        out['bbox'][v] = (xs.min(), xs.max(), ys.min(), ys.max()) if ys.size else (w, -1, h, -1)
+        d = depth[v][mask[v] > 0]
+        d = d[(d > np.float32(1e-3)) & (d < np.float32(1e4))]
+        if d.size:
+            out['depth_min'][v], out['depth_max'][v] = d.min(), d.max()
+    return out
+
+
+def _uni(lo, hi, u, T):
+    return T(lo) + (T(hi) - T(lo)) * T(u)
+
+
+def augment_numpy(depth, mask, depth_range, host, key, view0, rfn, dtype=np.float32, depth_range_aug=None):
+    """The reference of neuray_augment_depth (include/neuray_hip.h states the formulas): depth / mask [n,h,w], depth_range [n,2], host:
+    augment_host_numbers' array, key: (seed, batch index), the working views are [view0, view0 + rfn) -> dict(stats, depth_range_aug
+    [n,2], depth_range [n,2], plan [rfn,2,8], depth_aug [rfn,h,w]) in `dtype`, every operation in the kernel's order.  depth_range_aug:
+    use these ranges as the result of step 1 (a test hands over the kernel's own, so that what follows can be compared bit for bit).  The
+    centre's rank is evaluated in float32 in either dtype: it selects a pixel."""
+    T = np.dtype(dtype).type
+    mask, depth = np.asarray(mask), np.asarray(depth, np.float32)
+    n, h, w = mask.shape
+    H = np.asarray(host, np.float32).reshape(-1, AUG_HOST)
+    st = stats_numpy(mask, depth)
+    near, far = np.asarray(depth_range, np.float32)[:, 0].astype(T), np.asarray(depth_range, np.float32)[:, 1].astype(T)
+    # 1. the range augmentation
+    part = np.isfinite(st['depth_min'])
+    if H[0, 0] != 0 and part.any():
+        far_ratio = np.max((st['depth_max'][part].astype(T) * T(1.1)) / far[part])
+        near_ratio = np.max(near[part] / (st['depth_min'][part].astype(T) * T(0.9)))
+        if far_ratio < 1:
+            far = far * _uni(far_ratio, 1.0, H[0, 1], T)
+        if near_ratio < 1:
+            near = near / _uni(near_ratio, 1.0, H[0, 2], T)
+    if H[0, 3] != 0:
+        near, far = near * (T(1) - _uni(0.025, 0.1, H[0, 4], T)), far * (T(1) + _uni(0.025, 0.1, H[0, 5], T))
+    if depth_range_aug is not None:
+        near, far = np.asarray(depth_range_aug)[:, 0].astype(T), np.asarray(depth_range_aug)[:, 1].astype(T)
+    range_aug = np.stack([near, far], -1)
+    # 2. the depth noise of the working views
+    plan, depth_aug = np.zeros((rfn, 2, 8), T), np.zeros((rfn, h, w), T)
+    ys, xs = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')
+    for r in range(rfn):
+        v = view0 + r
+        L = far[v] - near[v]
+        d, fg, count = depth[v].astype(T), mask[v] > 0, int(st['count'][v])
+        xmin, xmax, ymin, ymax = (int(b) for b in st['bbox'][v])
+        for k in range(2):
+            R = H[1 + r, 6 * k: 6 * k + 6]
+            plan[r, k, 7] = L
+            if R[0] == 0 or count == 0:
+                continue
+            rank = min(int(np.float32(R[1]) * np.float32(count)), count - 1)
+            cy, cx = divmod(int(np.flatnonzero(fg)[rank]), w)
+            rmin, rmax, omin, omax, amp = (H[0, 8:13] if k == 0 else _SMALL_REGION)
+            lx, ly = _uni(rmin, rmax, R[2], T) * T(xmax - xmin), _uni(rmin, rmax, R[3], T) * T(ymax - ymin)
+            off = _uni(omin, omax, R[4], T) * L
+            if R[5] != 0:
+                off = -off
+            plan[r, k] = [1, cx, cy, lx, ly, off, T(amp), L]
+            region = fg & (np.abs((xs - cx).astype(T)) < lx) & (np.abs((ys - cy).astype(T)) < ly)
+            unit = (_pixel_words(h, w, v, k, key)[:, 0] >> np.uint32(8)).astype(T).reshape(h, w) * T(2.0 ** -24)
+            d = np.where(region, d + ((((T(2) * unit - T(1)) * T(amp)) * L) + off), d)
+        if H[1 + r, 12] != 0:
+            unit = (_pixel_words(h, w, v, 2, key)[:, 0] >> np.uint32(8)).astype(T).reshape(h, w) * T(2.0 ** -24)
+            d = d + ((T(2) * unit - T(1)) * T(0.005)) * L
+        depth_aug[r] = d
+    # 3. consistent_depth_range (the use_consistent_min_max: False branch)
+    if H[0, 6] != 0:
+        length = far - near
+        max_len = np.max(length)
+        near = np.maximum(near - (max_len - length) / T(2), near * T(0.5))
+        far = near + max_len
+    return {'stats': st, 'depth_range_aug': range_aug, 'depth_range': np.stack([near, far], -1), 'plan': plan, 'depth_aug': depth_aug}
+
+
+def sample_coords_numpy(mask, ray_num, foreground_ratio, key, view=0):
+    """The reference of neuray_sample_coords: a uniform draw without replacement as the k smallest of independent random keys.  mask
+    [h,w] -> coords [1,ray_num,2] float32 (x, y): the min(int(ray_num * foreground_ratio), foreground) foreground pixels with the
+    smallest (word0 << 32) | p, then the rest with the smallest (word1 << 32) | p among all pixels not yet picked, each part in row-major
+    order (p = y * w + x; the words: the pixel's purpose-3 Philox block)."""
+    fg = np.asarray(mask) > 0
+    h, w = fg.shape
+    if not 1 <= ray_num <= h * w:
+        raise ValueError("neuray_amd.procedural: ray_num=%d outside [1, h*w=%d]" % (ray_num, h * w))
+    words = _pixel_words(h, w, view, 3, key).astype(np.uint64)
+    p = np.arange(h * w, dtype=np.uint64)
+    c1, c2 = (words[:, 0] << np.uint64(32)) | p, (words[:, 1] << np.uint64(32)) | p
+    cand = np.flatnonzero(fg.reshape(-1))
+    k1 = min(int(ray_num * foreground_ratio), cand.size)
+    pick1 = np.sort(cand[np.argsort(c1[cand], kind='stable')[:k1]])
+    left = np.ones(h * w, bool)
+    left[pick1] = False
+    pool = np.flatnonzero(left)
+    pick2 = np.sort(pool[np.argsort(c2[pool], kind='stable')[:ray_num - k1]])
+    pix = np.concatenate([pick1, pick2]).astype(np.int64)
+    return np.stack([pix % w, pix // w], -1)[None].astype(np.float32)
+
+
 # ---- a fresh scene per training step ---------------------------------------------------------------------------------------------------
 # offsets (azimuth, elevation) in degrees of the source views from the query view, before the seeded jitter
 _SRC_OFFS = [(-5, 5), (5, -5), (-10, -8), (10, 8), (-15, 12), (15, -12), (-20, -3), (20, 3), (-25, 15), (25, -15), (-30, 6), (30, -6),
@@ -390,12 +571,16 @@ class ProceduralStream:
     one by hand on random images): every batch a new scene and new cameras - 1 query view, `rfn` working views and `extra_src` further
     source views for the cost volumes -, rendered on the device by one kernel launch.  The host prepares the scene array, the poses, the
     inverse intrinsics, the ray coordinates and the neighbour table and uploads them from pinned memory without blocking; nothing is read
-    back."""
+    back.  augment: None / False - the sample as rendered (depth is true_depth, the range (2, 6), uniform rays); True or a dict of
+    AUGMENT_DEFAULTS keys - the reference's training augmentation on the device: augmented and consistent depth ranges, a noisy `depth`
+    beside the exact `true_depth`, half of the rays from the query view's foreground (three more entries, still nothing read back)."""
 
-    def __init__(self, device, seed=0, h=416, w=608, rfn=8, extra_src=4, rays=512, ss=1, background='white', engine=None):
+    def __init__(self, device, seed=0, h=416, w=608, rfn=8, extra_src=4, rays=512, ss=1, background='white', engine=None, augment=None):
         if rfn + extra_src > len(_SRC_OFFS):
             raise ValueError("neuray_amd.procedural: at most %d source views" % len(_SRC_OFFS))
         self.device = torch.device(device)
+        self.augment = augment_config(augment)       # None: the plain stream; else the reference's augmentation (DESIGN.md 4.23)
+        self.last_augment = None                     # with augmentation: the host numbers and the kernels' plan / ranges of the last batch
         self.seed, self.h, self.w, self.rfn, self.extra_src, self.rays, self.ss, self.background = seed, h, w, rfn, extra_src, rays, ss, background
         self.engine = engine if engine is not None else _fresh_engine(self.device)
         self.index = 0
@@ -408,6 +593,10 @@ class ProceduralStream:
 
     def host_batch(self, index):
         """what the host prepares for batch `index`: scene array, poses [1 + n_src,3,4] (the query view first), coords, nn_ids"""
+        return self._host_draws(index)[:4]
+
+    def _host_draws(self, index):
+        """host_batch and the batch's RandomState after its draws (the augmentation draws its numbers from there on)"""
         from .network.renderer import nearest_view_table
         rng = np.random.RandomState((self.seed * 1000003 + index) % (2 ** 32))
         scene = make_scene(int(rng.randint(0, 2 ** 31 - 1)), self.background)
@@ -417,12 +606,12 @@ class ProceduralStream:
         poses = np.stack([synthetic.look_at_pose(synthetic.sphere_pos(CAMERA_RADIUS, a, e)) for a, e in angles]).astype(np.float32)
         coords = np.stack([rng.randint(0, self.w, size=self.rays), rng.randint(0, self.h, size=self.rays)], -1)[None].astype(np.float32)
         nn_ids = nearest_view_table(poses[1:1 + self.rfn], poses[1:])[:, 1:4].astype(np.int64)          # (column 0: the view itself)
-        return scene, poses, coords, nn_ids
+        return scene, poses, coords, nn_ids, rng
 
     def __next__(self):
         index, dev = self.index, self.device
         self.index += 1
-        scene, poses, coords, nn_ids = self.host_batch(index)
+        scene, poses, coords, nn_ids, rng = self._host_draws(index)
         n, rfn = poses.shape[0], self.rfn
         t_scene, t_poses = _upload(scene, dev), _upload(poses, dev)
         Ks = _upload(np.repeat(self.K[None], n, 0), dev)
@@ -436,6 +625,17 @@ class ProceduralStream:
         ref.update({'masks': masks[1:1 + rfn], 'depth': depth[1:1 + rfn], 'true_depth': depth[1:1 + rfn], 'nn_ids': _upload(nn_ids, dev)})
         que = {'imgs': imgs[:1], 'poses': t_poses[:1], 'Ks': Ks[:1], 'Ks_inv': Ks_inv[:1], 'depth_range': rng_[:1], 'coords': _upload(coords, dev),
                'masks': masks[:1], 'depth': depth[:1]}
+        if self.augment is not None:
+            # (in the reference's order: ranges over all views, noise on the working views, consistent ranges, rays from the query mask)
+            key = (self.seed & _M32, index & _M32)
+            host = augment_host_numbers(rng, rfn, self.augment)
+            stats = self.engine.augment_stats(out['mask'], out['depth'])
+            aug = self.engine.augment_depth(out['depth'], out['mask'], rng_, stats, _upload(host, dev), key, 1, rfn)
+            final = aug['depth_range']
+            src['depth_range'], ref['depth_range'], que['depth_range'] = final[1:], final[1:1 + rfn], final[:1]
+            ref['depth'] = aug['depth_aug'][:, None]
+            que['coords'] = self.engine.sample_coords(out['mask'][0], self.rays, self.augment['foreground_ratio'], key, view=0)
+            self.last_augment = {'host': host, 'key': key, 'stats': stats, 'plan': aug['plan'], 'depth_range_aug': aug['depth_range_aug']}
         return {'que_imgs_info': que, 'ref_imgs_info': ref, 'src_imgs_info': src, 'scene_name': 'procedural/%d/%d' % (self.seed, index)}
 
 

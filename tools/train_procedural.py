@@ -4,7 +4,9 @@ ground truth - a NeuralRayFtRenderer trained from scratch on one procedural scen
     python tools/train_procedural.py --time
         kernel time (device events, median of 20 after warm-up) of one ProceduralStream batch - 13 views of 416 x 608, ss 1 and 2 - and of
         one 800 x 800 view, and the generalisation step of bench.gen_train_case fed by its fixed batch against the same step fed by the
-        stream, in one process.  One JSON line.
+        stream, in one process.  One JSON line.  With --augment additionally the kernel time per batch of the three augmentation entries
+        (augment_stats, augment_depth, sample_coords: DESIGN.md 4.23) next to the render launch of the same batch, and the generalisation
+        step fed by the augmented stream.
     python tools/train_procedural.py --scene procedural/0/white_800 --steps N
         trains every network of a NeuralRayFtRenderer on the scene's 42 training views (render + consistency loss of neuray_amd.loss, Adam),
         then renders the 6 held-out views with hip_arith f32 / x3 and the network coarse pass, and x3 with hip_coarse_pass = 'visibility':
@@ -62,7 +64,27 @@ def kernel_times(dev):
     return res
 
 
-def gen_step_times(dev, steps=10):
+def augment_times(dev, reps=20, warmup=3):
+    """device-event time per batch of every engine entry a ProceduralStream batch with augmentation launches (median of `reps`)"""
+    eng = render_ops.engine_for(dev)
+    stream = procedural.ProceduralStream(dev, seed=0, h=416, w=608, rfn=8, extra_src=4, rays=512, augment=True, engine=eng)
+    for _ in range(warmup):
+        next(stream)
+    per = {}
+    for _ in range(reps):
+        eng.timing = []
+        next(stream)
+        torch.cuda.synchronize(dev)
+        batch = {}
+        for name, e0, e1, _n in eng.timing:
+            batch[name] = batch.get(name, 0.0) + e0.elapsed_time(e1)
+        for name, ms in batch.items():
+            per.setdefault(name, []).append(ms)
+    eng.timing = None
+    return {'augment_batch_13x416x608_%s_ms' % ('render' if k == 'procedural' else k): float(np.median(v)) for k, v in per.items()}
+
+
+def gen_step_times(dev, steps=10, augment=False):
     """bench.gen_train_case's loop on its fixed batch, then the same model / optimiser / losses on a fresh stream batch per step"""
     import bench
     model, opt, step = bench.gen_train_case(dev, host_ks_inv=True)
@@ -94,9 +116,12 @@ def gen_step_times(dev, steps=10):
         loss = loss + ((d - out['depth_mean']) ** 2).mean() + ((d - out['depth_mean_fine']) ** 2).mean()
         loss.backward()
         opt.step()
-    streamed = timed(stream_step)
+    res = {'gen_step_fixed_batch_ms': fixed, 'gen_step_stream_ms': timed(stream_step)}
+    if augment:
+        stream = procedural.ProceduralStream(dev, seed=0, h=h, w=w, rfn=rfn, extra_src=4, rays=512, augment=True)
+        res['gen_step_stream_augment_ms'] = timed(stream_step)
     render_ops.check_deferred_inputs(dev, wait=True)
-    return {'gen_step_fixed_batch_ms': fixed, 'gen_step_stream_ms': streamed}
+    return res
 
 
 def evaluate(ft, db, val_ids, dev):
@@ -231,12 +256,15 @@ def main():
     ap.add_argument('--rays', type=int, default=512)
     ap.add_argument('--lr', type=float, default=1e-3)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--augment', action='store_true', help='--time: also the augmented stream (the three augmentation entries per batch)')
     ap.add_argument('--export-points', action='store_true', help='fuse the rendered depth of the training views in each render mode')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     if args.time:
         res = kernel_times(dev)
-        res.update(gen_step_times(dev))
+        if args.augment:
+            res.update(augment_times(dev))
+        res.update(gen_step_times(dev, augment=args.augment))
     else:
         res = train(args, dev)
     print(json.dumps(res))
