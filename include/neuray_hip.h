@@ -939,6 +939,38 @@ typedef struct NeuraySampleCoordsArgs {
 } NeuraySampleCoordsArgs;
 int neuray_sample_coords(const NeuraySampleCoordsArgs* args, void* stream);
 
+/* ---- plane-sweep stereo (neuray_amd/stereo.py; added within ABI 11: everything above is unchanged).  Posed images and a depth
+ * range per view -> a depth map per view; the fp32 library only (the bf16-operand variants return an error), inference only.  The formulas
+ * are stereo.plane_sweep_numpy's: gray a = ((0.299 R + 0.587 G) + 0.114 B) - 0.5 of every view (written to gray_dev, a workspace of
+ * [n][h][w] floats); cams_dev [n][n_src][12] holds, per (view i, slot s) with j = nn_ids[i][s] (-1 or i itself: an unused slot), M = K_j R_rel
+ * K_i^-1 row-major and b = K_j t_rel (stereo.sweep_constants: float64 rounded to float32), so that pixel (x, y) of view i on the plane of
+ * depth d projects to q = d (M (x, y, 1)) + b, (u, v) = q.xy / q.z in view j; `planes` (3 .. NEURAY_SWEEP_MAX_PLANES) planes per view,
+ * uniform in inverse depth between depth_range_dev [n][2] = near, far (t = k / (planes - 1), 1 / d_k = (1 - t) / near + t / far); per source
+ * the cost 1 - ZNCC over the (2 radius + 1)^2 window (radius 1 .. 3) of the reference gray and the bilinearly warped source gray, valid where
+ * the whole window lies inside the reference image, every warp has q.z > 0 and lands in [0, w-1] x [0, h-1], and both variances are >=
+ * var_min; per plane the mean of the ceil(m / 2) smallest of the m valid costs, invalid where m < min_src (min_src = 0: 2, or 1 for a view
+ * with one used slot); the plane of the lowest cost wins (ties: the lowest index) and is refined by the parabola through its neighbours'
+ * costs (where both are valid and the second difference exceeds 1e-2; the offset clipped to +-0.5).  The views [v0, v1) are swept in one
+ * launch; the outputs hold v1 - v0 views: depth_dev (0 = none), cost_dev (NEURAY_SWEEP_COST_NONE = none), plane_dev (-1 = none).  flags bit
+ * 0: do not skip the (tile, plane, source) triples whose tile projects outside the source (same bits either way).  No atomics: two calls
+ * and any split of the views over calls give the same bits. */
+#define NEURAY_SWEEP_MAX_PLANES 256
+#define NEURAY_SWEEP_COST_NONE 4.0f
+#define NEURAY_SWEEP_NO_SKIP 1
+typedef struct NeurayPlaneSweepArgs {
+    const float* imgs_dev;             /* [n][3][h][w] in [0,1] */
+    float* gray_dev;                   /* [n][h][w] workspace */
+    const float* cams_dev;             /* [n][n_src][12] */
+    const float* depth_range_dev;      /* [n][2] */
+    const int* nn_ids_dev;             /* [n][n_src] */
+    float* depth_dev;                  /* [v1 - v0][h][w] */
+    float* cost_dev;                   /* [v1 - v0][h][w] */
+    int* plane_dev;                    /* [v1 - v0][h][w] */
+    int n, h, w, n_src, planes, radius, v0, v1, min_src, flags;
+    float var_min, reserved_f;
+} NeurayPlaneSweepArgs;
+int neuray_plane_sweep(const NeurayPlaneSweepArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

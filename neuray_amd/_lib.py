@@ -160,6 +160,13 @@ class NeuraySampleCoordsArgs(C.Structure):
         [(n, C.c_int) for n in ('h', 'w', 'ray_num', 'want_fg', 'view', 'reserved')] + [('key0', C.c_uint), ('key1', C.c_uint)]
 
 
+class NeurayPlaneSweepArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('imgs_dev', 'gray_dev', 'cams_dev', 'depth_range_dev', 'nn_ids_dev', 'depth_dev', 'cost_dev', 'plane_dev')] + \
+        [(n, C.c_int) for n in ('n', 'h', 'w', 'n_src', 'planes', 'radius', 'v0', 'v1', 'min_src', 'flags')] + \
+        [('var_min', C.c_float), ('reserved_f', C.c_float)]
+
+
+SWEEP_MAX_PLANES, SWEEP_COST_NONE, SWEEP_NO_SKIP = 256, 4.0, 1   # include/neuray_hip.h NEURAY_SWEEP_*
 AUGMENT_STATS, AUGMENT_PLAN, AUGMENT_HOST, SAMPLE_COORDS_WORK = 8, 8, 16, 16416   # include/neuray_hip.h NEURAY_AUGMENT_*, NEURAY_SAMPLE_COORDS_WORK
 TSDF_BLOCK = 8                # cells per block and axis (neuray_surface_blocks)
 TSDF_MAX_POINTS = 1 << 30      # nx * ny * nz of a volume (include/neuray_hip.h)
@@ -315,6 +322,8 @@ SYMBOLS = {
     'neuray_augment_stats': (C.c_int, [C.POINTER(NeurayAugmentStatsArgs), C.c_void_p]),
     'neuray_augment_depth': (C.c_int, [C.POINTER(NeurayAugmentDepthArgs), C.c_void_p]),
     'neuray_sample_coords': (C.c_int, [C.POINTER(NeuraySampleCoordsArgs), C.c_void_p]),
+    # plane-sweep stereo
+    'neuray_plane_sweep': (C.c_int, [C.POINTER(NeurayPlaneSweepArgs), C.c_void_p]),
 }
 
 

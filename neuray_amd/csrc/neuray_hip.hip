@@ -23,6 +23,7 @@
 #include "nr_kernels_fuse.h"        // (the fp32 library only, like the visibility entries)
 #include "nr_kernels_tsdf.h"        // (likewise)
 #include "nr_kernels_aug.h"         // (likewise)
+#include "nr_kernels_stereo.h"      // (likewise)
 #endif
 #include "nr_pack.h"
 #include "../../include/neuray_hip.h"
@@ -1694,6 +1695,50 @@ int neuray_tsdf_raycast(const NeurayTsdfRaycastArgs* a, void* stream) {
     if (grid.y > 65535u) return fail("neuray_tsdf_raycast: h=%d too large (at most %d)", a->h, 65535 * nr::kRaycastTileY);
     NR_LAUNCH(nr::tsdf_raycast_kernel, grid, dim3(nr::kRaycastTileX * nr::kRaycastTileY), 0, stream, p);
     return check_launch("neuray_tsdf_raycast");
+#endif
+}
+
+// ---- plane-sweep stereo ----
+#ifndef NR_BF16_QUADS
+extern "C++" {
+template <int R>
+static void launch_plane_sweep(const nr::SweepParams& p, dim3 grid, void* stream) {
+    // the smallest costs kept per plane: ceil(S / 2) of them enter the mean
+    if (p.S <= 4) NR_LAUNCH((nr::plane_sweep_kernel<R, 2>), grid, dim3(nr::kSweepThreads), 0, stream, p);
+    else if (p.S <= 8) NR_LAUNCH((nr::plane_sweep_kernel<R, 4>), grid, dim3(nr::kSweepThreads), 0, stream, p);
+    else NR_LAUNCH((nr::plane_sweep_kernel<R, 8>), grid, dim3(nr::kSweepThreads), 0, stream, p);
+}
+}  // extern "C++"
+#endif
+
+int neuray_plane_sweep(const NeurayPlaneSweepArgs* a, void* stream) {
+#ifdef NR_BF16_QUADS
+    (void)a; (void)stream;
+    return fail("neuray_plane_sweep: lives in the fp32 library (this is a bf16-operand variant build)");
+#else
+    if (!a) return fail("neuray_plane_sweep: null args");
+    if (a->radius < 1 || a->radius > nr::kSweepMaxRadius) return fail("neuray_plane_sweep: radius=%d outside [1,%d]", a->radius, nr::kSweepMaxRadius);
+    if (a->n < 1 || a->h < 2 * a->radius + 1 || a->w < 2 * a->radius + 1) return fail("neuray_plane_sweep: bad size n=%d h=%d w=%d (radius %d)", a->n, a->h, a->w, a->radius);
+    if (a->n_src < 1 || a->n_src > nr::kSweepMaxSrc) return fail("neuray_plane_sweep: n_src=%d outside [1,%d]", a->n_src, nr::kSweepMaxSrc);
+    if (a->planes < 3 || a->planes > NEURAY_SWEEP_MAX_PLANES) return fail("neuray_plane_sweep: planes=%d outside [3,%d]", a->planes, NEURAY_SWEEP_MAX_PLANES);
+    if (a->v0 < 0 || a->v1 <= a->v0 || a->v1 > a->n) return fail("neuray_plane_sweep: views [%d,%d) of %d", a->v0, a->v1, a->n);
+    if (a->min_src < 0 || !(a->var_min > 0.0f)) return fail("neuray_plane_sweep: min_src=%d var_min=%g", a->min_src, a->var_min);
+    if ((long long)a->h * a->w > 0x7fffffffLL || (long long)a->n * a->n_src > 0x7ffffffLL) return fail("neuray_plane_sweep: h*w or n*n_src too large");
+    const unsigned gx = (unsigned)((a->w + nr::kSweepTile - 1) / nr::kSweepTile), gy = (unsigned)((a->h + nr::kSweepTile - 1) / nr::kSweepTile);
+    if (a->v1 - a->v0 > 65535 || gy > 65535u) return fail("neuray_plane_sweep: %d views of height %d are too many for one call", a->v1 - a->v0, a->h);
+    if (!a->imgs_dev || !a->gray_dev || !a->cams_dev || !a->depth_range_dev || !a->nn_ids_dev) return fail("neuray_plane_sweep: imgs / gray / cams / depth_range / nn_ids missing");
+    if (!a->depth_dev || !a->cost_dev || !a->plane_dev) return fail("neuray_plane_sweep: depth / cost / plane missing");
+    nr::SweepParams p;
+    p.rgb = a->imgs_dev; p.gray = a->gray_dev; p.cams = a->cams_dev; p.range = a->depth_range_dev; p.nn_ids = a->nn_ids_dev;
+    p.depth = a->depth_dev; p.cost = a->cost_dev; p.plane = a->plane_dev;
+    p.n = a->n; p.h = a->h; p.w = a->w; p.S = a->n_src; p.D = a->planes; p.v0 = a->v0; p.v1 = a->v1; p.min_src = a->min_src; p.flags = a->flags;
+    p.var_min = a->var_min;
+    NR_LAUNCH(nr::sweep_gray_kernel, dim3((unsigned)grid_for((long long)a->n * a->h * a->w, 256, 65536)), dim3(256), 0, stream, p);
+    const dim3 grid(gx, gy, (unsigned)(a->v1 - a->v0));
+    if (a->radius == 1) launch_plane_sweep<1>(p, grid, stream);
+    else if (a->radius == 2) launch_plane_sweep<2>(p, grid, stream);
+    else launch_plane_sweep<3>(p, grid, stream);
+    return check_launch("neuray_plane_sweep");
 #endif
 }
 

@@ -1140,6 +1140,43 @@ class RenderEngine:
         self._event_done(ev, 'fuse_view', h * w)
         return out
 
+    # ---- plane-sweep stereo (neuray_amd/stereo.py) ----
+    def plane_sweep(self, imgs, poses, Ks, depth_range, nn_ids, planes=128, radius=2, var_min=None, min_src=None, views=None, skip=True):
+        """Depth maps of posed images by plane sweep, all views of the call in one launch (include/neuray_hip.h, neuray_plane_sweep).
+        imgs [n,3,h,w] in [0,1], poses [n,3,4], Ks [n,3,3], depth_range [n,2], nn_ids [n,S] (-1 or the view itself: an unused slot);
+        views: (v0, v1), sweep only those -> dict of device tensors over the swept views: depth [.,h,w] float32 (0 = none), cost [.,h,w]
+        float32 (stereo.COST_NONE = none), plane [.,h,w] int32 (-1 = none).  The per-(view, slot) constants are made on the host from the
+        cameras (stereo.sweep_constants: hand cameras over as host arrays to avoid a read-back); no host synchronisation otherwise.
+        skip=False: also run the (tile, plane, source) triples that project outside the source (the same bits)."""
+        from . import stereo
+        if self.variant != 'fp32':
+            raise NotImplementedError("neuray_amd: the plane sweep lives in the fp32 library (variant=%r)" % (self.variant,))
+        host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)     # noqa: E731
+        imgs = torch.as_tensor(imgs)
+        if imgs.dim() != 4 or imgs.shape[1] != 3:
+            raise ValueError("neuray_amd.stereo: imgs [n,3,h,w], got %s" % (tuple(imgs.shape),))
+        n, _, h, w = imgs.shape
+        poses_h, Ks_h, rng_h, nn_h = stereo._check_cameras(n, *(host(a) for a in (poses, Ks, depth_range, nn_ids)))
+        S = nn_h.shape[1]
+        stereo._check_sizes(n, h, w, int(planes), radius, S)
+        v0, v1 = (0, n) if views is None else (int(views[0]), int(views[1]))
+        if not 0 <= v0 < v1 <= n:
+            raise ValueError("neuray_amd.stereo: views [%d, %d) of %d" % (v0, v1, n))
+        imgs = self._f32(imgs)
+        cams = torch.from_numpy(stereo.sweep_constants(poses_h, Ks_h, nn_h)).to(self.device)
+        rng = torch.from_numpy(np.ascontiguousarray(rng_h, dtype=np.float32)).to(self.device)
+        nn = torch.from_numpy(nn_h.astype(np.int32)).to(self.device)
+        gray = self.empty(n, h, w)
+        out = {'depth': self.empty(v1 - v0, h, w), 'cost': self.empty(v1 - v0, h, w), 'plane': self.empty(v1 - v0, h, w, dtype=torch.int32)}
+        a = _lib.NeurayPlaneSweepArgs(imgs.data_ptr(), gray.data_ptr(), cams.data_ptr(), rng.data_ptr(), nn.data_ptr(), out['depth'].data_ptr(),
+                                      out['cost'].data_ptr(), out['plane'].data_ptr(), n, h, w, S, int(planes), int(radius), v0, v1,
+                                      int(min_src or 0), 0 if skip else _lib.SWEEP_NO_SKIP,
+                                      float(stereo.VAR_MIN if var_min is None else var_min), 0.0)
+        ev = self._event_pair()
+        self._check(self.lib.neuray_plane_sweep(C.byref(a), self._stream()))
+        self._event_done(ev, 'plane_sweep', (v1 - v0) * h * w)
+        return out
+
     # ---- mesh export (neuray_amd/mesh.py, DESIGN.md 4.21) ----
     def _tsdf_state(self, state, dims):
         """state: dict of device tensors tsum / w [nz,ny,nx] and optionally csum [3,nz,ny,nx] / cw [nz,ny,nx] -> (nx, ny, nz), has colour"""

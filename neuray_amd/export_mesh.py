@@ -1,10 +1,10 @@
 """Mesh export from the command line (neuray_amd/mesh.py):
 
-    python -m neuray_amd.export_mesh --database NAME --depth database|render [--cfg CFG --ckpt CKPT] --voxel V --out mesh.ply
+    python -m neuray_amd.export_mesh --database NAME --depth database|render|stereo [--cfg CFG --ckpt CKPT] --voxel V --out mesh.ply
                                      [--trunc T --min-weight 1 --no-filter --src 8 --tau-px 1 --tau-d 0.01 --min-views 2 --json out.json]
                                      [--raycast DIR --step 0.5]
 
-fuses the depth maps of every view of a database - its own (`--depth database`), or the `render_depth_fine` of a renderer that renders each
+fuses the depth maps of every view of a database - its own (`--depth database`), plane-sweep stereo of its images (`--depth stereo`, neuray_amd.stereo), or the `render_depth_fine` of a renderer that renders each
 view from its nearest other views (`--depth render`, as neuray_amd.export_points) - into a truncated signed distance field of voxel size V
 (default: 256 lattice points on the longest side of the depths' bounding box) and writes its zero surface as a binary PLY with normals,
 colours and triangles.  The printed line carries the vertex count, the face count and the number of boundary edges (0: the surface is closed)
@@ -39,6 +39,9 @@ def export(args):
     ids = db.get_img_ids()
     if args.depth == 'database':
         maps = geometry.database_depth_maps(db, ids)
+    elif args.depth == 'stereo':
+        from . import stereo
+        maps = stereo.stereo_depth_maps(db, ids)
     else:
         if not args.cfg:
             raise SystemExit("neuray_amd.export_mesh: --depth render needs --cfg (and usually --ckpt)")
@@ -321,7 +324,7 @@ def timing(n=48, size=800, points=256, eager_reps=3):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     ap.add_argument('--database', type=str, default=None, help="e.g. procedural/0/white_800")
-    ap.add_argument('--depth', choices=('database', 'render'), default='database')
+    ap.add_argument('--depth', choices=('database', 'render', 'stereo'), default='database')
     ap.add_argument('--cfg', type=str, default=None)
     ap.add_argument('--ckpt', type=str, default=None)
     ap.add_argument('--out', type=str, default='mesh.ply')

@@ -1,9 +1,9 @@
 """Geometry export from the command line (neuray_amd/geometry.py):
 
-    python -m neuray_amd.export_points --database NAME --depth database|render [--cfg CFG --ckpt CKPT] --out cloud.ply
+    python -m neuray_amd.export_points --database NAME --depth database|render|stereo [--cfg CFG --ckpt CKPT] --out cloud.ply
                                        [--src 8 --tau-px 1 --tau-d 0.01 --min-views 2 --tau-n 0.05 --no-dedup --json out.json]
 
-fuses the depth maps of every view of a database - its own (`--depth database`), or the `render_depth_fine` of a renderer that renders each
+fuses the depth maps of every view of a database - its own (`--depth database`), plane-sweep stereo of its images (`--depth stereo`, neuray_amd.stereo), or the `render_depth_fine` of a renderer that renders each
 view from its nearest other views (`--depth render`; --cfg: the renderer's cfg as JSON, or YAML where PyYAML is installed, --ckpt: its
 weights, a state_dict or a checkpoint with 'network_state_dict') - into one point cloud and writes it as a binary PLY with normals and
 colours.  For a procedural scene the printed line carries the distance of the points to the true surface.
@@ -55,6 +55,9 @@ def export(args):
     ids = db.get_img_ids()
     if args.depth == 'database':
         maps = geometry.database_depth_maps(db, ids)
+    elif args.depth == 'stereo':
+        from . import stereo
+        maps = stereo.stereo_depth_maps(db, ids)
     else:
         if not args.cfg:
             raise SystemExit("neuray_amd.export_points: --depth render needs --cfg (and usually --ckpt)")
@@ -221,7 +224,7 @@ def timing(n=48, size=800, src=8, eager_reps=3):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
     ap.add_argument('--database', type=str, default=None, help="e.g. procedural/0/white_800")
-    ap.add_argument('--depth', choices=('database', 'render'), default='database')
+    ap.add_argument('--depth', choices=('database', 'render', 'stereo'), default='database')
     ap.add_argument('--cfg', type=str, default=None)
     ap.add_argument('--ckpt', type=str, default=None)
     ap.add_argument('--out', type=str, default='cloud.ply')
